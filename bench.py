@@ -1,8 +1,20 @@
 """Benchmark of the encode -> 8-bit quantize -> synthesize path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c2g|c2r|c4|c5] [--batch B]
-                    [--precision f16|bf16|bf16-all|fp32] [--no-roofline] [--no-parity] [--cpu-baseline-images M]
-                    [--dry-run]
+                    [--precision f16|bf16|bf16-all|fp32] [--dump-outputs DIR] [--dry-run]
+                    [--full [--no-roofline] [--no-parity] [--no-secondary] [--cpu-baseline-images M]]
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, the outputs of the last
+timed step if --dump-outputs is given, and the result line.  --full adds the untimed legs to that line, each in a pass
+of its own after the headline loop: the per-kernel roofline, the parity record, the secondary C4 entry of the default
+c2 line and the CPU baseline (--no-roofline, --no-parity, --no-secondary and --cpu-baseline-images 0 drop single legs
+of a --full run).
+
+--dump-outputs DIR (rank 0): what the last timed step handed back, as DIR/<name>.npy -- `codes` (the quantized
+latents, or the codebook indices of c2g), `image` (the reconstruction, float32) and `record` (the all-reduced fp64
+metric record); c5: `record` (the step's summed losses) alone.  Inputs and weights are seeded, so two builds run with
+the same arguments are comparable array by array.  An array above DUMP_MAX_BYTES is written as a fixed seeded sample
+of its elements (flat indices drawn with seed DUMP_SEED, in ascending order).
 
 A step = one pass of the hot path over one synthetic batch already resident in HBM:
 HVAE_VGG_Encoder(img_resolution=1024) on 256^2 images -> 8-bit uniform quantizer (deterministic, means)
@@ -18,7 +30,7 @@ tests/test_gpu_c2_parity.py); bf16 = split-bf16 encoder + bf16 synthesis (meets 
 bf16-all = bf16 encoder + bf16 synthesis (round 2's mode: 4.6 % of the 8-bit indices differ from the reference's);
 fp32 = the exact-fp32 parity mode.
 
-Parity in the line (rank 0, outside the timed region; --no-parity skips it): 'parity' holds the benched encoder's
+Parity in the line (--full; rank 0, outside the timed region; --no-parity skips it): 'parity' holds the benched encoder's
 8-bit indices against the committed fp32 oracle means of the same input images (tests/golden/parity_means.npz,
 made by tests/golden/make_parity_means.py) and the north-star PSNR deltas of the benched images at the 34 dB and
 46 dB operating points, against the fp32 HIP path on the same latents and against the reconstruction of the
@@ -41,7 +53,7 @@ barrier / max-over-ranks timing and reductions on the CPU over gloo with a stand
 Timing protocol: W untimed warm-up steps, then EXACTLY K steps bracketed by a barrier +
 synchronize on both sides; value = images of all ranks / the max over ranks of that wall time.  Each timed
 step is also bracketed by HIP events on the launching stream (torch's current stream, which every libic2ops
-kernel is enqueued on): ms_per_step_median.  The per-kernel roofline timers run in a SEPARATE instrumented
+kernel is enqueued on): ms_per_step_median.  The per-kernel roofline timers (--full) run in a SEPARATE instrumented
 pass after the headline loop, so the headline number carries no instrumentation.  Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
@@ -87,6 +99,9 @@ BF16_PEAK_TFLOPS = 2500.0   # dense bf16 MFMA, MI355X_MICROARCH.md
 F32_PEAK_TFLOPS = 157.3     # f32 MFMA / VALU
 HBM_PEAK_GBS = 8000.0
 N_CODES = 256               # 8-bit codes: the record's histogram width
+DUMP_MAX_BYTES = 24 << 20   # --dump-outputs: per array, larger ones are sampled (the C2 image, 24 MiB, goes out whole;
+                            # only codes and image can reach the cap, so a dump stays below 64 MB in all)
+DUMP_SEED = 1234
 
 CONV_ENTRIES = ("ic2_conv_igemm_ws", "ic2_conv3x3_gn_fwd", "ic2_conv3x3_gn_fwd_scaled", "ic2_conv3x3_gnin_gn_fwd",
                 "ic2_from_rgb_conv", "ic2_from_rgb_conv_x3", "ic2_from_rgb_conv_f16", "ic2_conv_wino")
@@ -102,11 +117,17 @@ def parse(argv=None):
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the config's)")
     ap.add_argument("--precision", default=DEFAULT_PRECISION, choices=sorted(PRECISIONS))
-    ap.add_argument("--cpu-baseline-images", type=int, default=3, help="0 disables the CPU baseline leg")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity record (rank 0, untimed)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop, also run the untimed legs: per-kernel roofline, parity record, "
+                         "secondary C4 entry, CPU baseline (the --no-* options and --cpu-baseline-images 0 drop "
+                         "single legs of such a run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--cpu-baseline-images", type=int, default=3, help="--full: 0 disables the CPU baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the instrumented roofline pass")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the parity record (rank 0, untimed)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the untimed secondary C4 entry of the default c2 line (rank 0, N=1)")
+                    help="--full: skip the untimed secondary C4 entry of the default c2 line (rank 0, N=1)")
     ap.add_argument("--dry-run", action="store_true", help="CPU / gloo rehearsal of launcher + timing + reductions")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file (rank 0)")
     return ap.parse_args(argv)
@@ -487,6 +508,22 @@ def record_summary(vec, n_codes=N_CODES):
             "hist_nonzero_bins": int((hist > 0).sum())}
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor of `arrays` as path/<name>.npy, float32 (float64 stays float64).  A tensor above
+    DUMP_MAX_BYTES is written as the elements at fixed flat indices (drawn with DUMP_SEED, ascending): the same
+    elements on every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        t = t if t.dtype == torch.float64 else t.float()
+        keep = DUMP_MAX_BYTES // t.element_size()
+        if t.numel() > keep:
+            idx = torch.randint(t.numel(), (keep,), generator=torch.Generator().manual_seed(DUMP_SEED))
+            t = t.reshape(-1)[idx.sort().values]
+        np.save(os.path.join(path, name + ".npy"), t.contiguous().numpy())
+
+
 def run(args):
     dry = args.dry_run
     # rehearsal of the N > 1 path on a one-GPU box: every rank on cuda:0, collectives over gloo (not a measurement)
@@ -507,6 +544,7 @@ def run(args):
         dev = torch.device("cuda", local)
         sync = torch.cuda.synchronize
     barrier = lambda: icd.barrier(dev)
+    last = {}   # what the latest step handed back (references, no copy): written out by --dump-outputs
 
     if dry:
         # stand-in step: the same seeded per-rank batch, a metric record (SSE, counts, 8-bit code histogram of
@@ -521,7 +559,9 @@ def run(args):
             sse = float(om.sse_uint8(x, x.flip(0)).sum())
             hist = torch.bincount(codes.clamp(0, N_CODES - 1), minlength=N_CODES).double()
             vec = torch.cat([torch.tensor([sse, float(x.numel()), float(batch), 0.0, 0.0], dtype=torch.float64), hist])
-            return icd.allreduce_sum(vec)
+            vec = icd.allreduce_sum(vec)
+            last.update(record=vec)
+            return vec
         enc = G = comp = nv = None
     else:
         import image_compression_2_amd as ic2
@@ -561,7 +601,9 @@ def run(args):
                                         scaler=scaler)
                 vec = torch.cat([(losses["rec_loss"].double() * batch).view(1),
                                  (losses["kl_loss"].double() * batch).view(1), counts[1:]])
-                return icd.allreduce_sum(vec, device=dev)
+                vec = icd.allreduce_sum(vec, device=dev)
+                last.update(record=vec)
+                return vec
 
         def code_record(codes, kind):
             """[index mismatches vs the first step's codes, out-of-range codes, hist[256]] (ic2_code_record)."""
@@ -584,14 +626,16 @@ def run(args):
                     img = comp.decompress(codes)
                     rec = code_record(codes, 1)
                 else:
-                    q = comp.compress(x, quantization_bits=8, deterministic=True)
-                    img = comp.decompress(q)
-                    rec = code_record(q, 0)
+                    codes = comp.compress(x, quantization_bits=8, deterministic=True)
+                    img = comp.decompress(codes)
+                    rec = code_record(codes, 0)
                 if img.shape[2] != res:
                     img = ic2.resize_bilinear(img, (res, res))
                 sse = icm.uint8_sse(img, x)
             vec = torch.cat([sse.sum().view(1), counts, rec])
-            return icd.allreduce_sum(vec, device=dev)
+            vec = icd.allreduce_sum(vec, device=dev)
+            last.update(codes=codes, image=img, record=vec)
+            return vec
 
     if not dry and args.config == "c5":
         step = train_step
@@ -603,6 +647,9 @@ def run(args):
     median_ms = statistics.median(per_step)
     median_max = icd.allreduce_max(median_ms, device=dev)
     checksum = icd.allgather_floats(float(x.double().sum()), device=dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)   # before any --full leg runs the step again
+    last.clear()
 
     total_images = batch * args.steps * world
     value = total_images / elapsed_max
@@ -660,17 +707,19 @@ def run(args):
         if args.config == "c2g":
             out["config"]["quantizer"] = "GumbelSoftmaxCompressor (linspace(-1,1,256) codebook, exact argmin)"
 
-    if not dry and not args.no_roofline:
+    full = args.full and not dry   # the untimed legs below run only on request
+    if full and not args.no_roofline:
         out["roofline"] = roofline(args, nv, step, sync, barrier, enc, G, res, batch, value / world, enc_prec,
                                    syn_prec)
-    if not dry and rank == 0 and not args.no_parity and args.config in ("c2", "c2g", "c4"):
+    if full and rank == 0 and not args.no_parity and args.config in ("c2", "c2g", "c4"):
         out["parity"] = parity_record(args, comp, enc, G, x, x_host, res, syn_prec)
 
-    if not dry and rank == 0 and world == 1 and args.config == "c2" and not args.no_secondary:
+    if full and rank == 0 and world == 1 and args.config == "c2" and not args.no_secondary:
         # the headline models are done: free them before the C4 models are built, and never let the secondary
         # measurement (an OOM, a parity assertion) cost the headline line
         import gc
         comp = enc = G = step = None
+        last.clear()
         gc.collect()
         torch.cuda.empty_cache()
         try:
@@ -679,7 +728,7 @@ def run(args):
             out["secondary"] = {"c4": {"error": f"{type(e).__name__}: {e}"[:500]}}
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and args.cpu_baseline_images > 0 and not dry:
+    if full and rank == 0 and world == 1 and args.cpu_baseline_images > 0:
         if args.config == "c5":
             out["cpu_baseline"] = cpu_baseline_train(res, gen_res, 1)
         elif args.config in ("c2r", "c4"):

@@ -63,6 +63,39 @@ def test_single_rank_dry_run():
     assert rec["n_gpus"] == 1 and rec["world_size"] == 1 and len(rec["per_rank_ms_per_step"]) == 1
 
 
+def test_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs writes the last timed step's record (the dry run's only output) as float64 .npy; a plain line
+    carries none of the --full legs."""
+    import numpy as np
+    rec = _run(["--dry-run", "--steps", "2", "--warmup", "0", "--batch", "2", "--dump-outputs", str(tmp_path / "d")])
+    assert sorted(os.listdir(tmp_path / "d")) == ["record.npy"]
+    vec = np.load(tmp_path / "d" / "record.npy")
+    assert vec.dtype == np.float64 and vec.shape == (5 + 256,)
+    assert vec[1] == 2 * 3 * 16 * 16 and vec[2] == 2 and vec[5:].sum() == rec["metric_record"]["hist_sum"]
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert not {"roofline", "parity", "secondary", "cpu_baseline"} & set(rec)
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """An array above the per-array cap is written as a fixed seeded sample of its elements, the same on every call;
+    smaller ones whole, float32 unless float64."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 1000)
+    big = torch.arange(5000, dtype=torch.int32).reshape(50, 100)
+    arrays = {"big": big, "small": torch.arange(12, dtype=torch.int64).reshape(3, 4),
+              "f64": torch.linspace(0, 1, 7, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert a["big"].dtype == np.float32 and a["big"].shape == (1000,)
+    assert np.all(np.diff(a["big"]) >= 0) and set(a["big"]) <= set(range(5000)) and len(set(a["big"])) > 500
+    assert a["small"].dtype == np.float32 and np.array_equal(a["small"], np.arange(12).reshape(3, 4))
+    assert a["f64"].dtype == np.float64 and np.array_equal(a["f64"], arrays["f64"].numpy())
+    for n in arrays:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy"))
+
+
 def test_gpus_mismatch_with_env_is_an_error():
     e = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29599")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"],
