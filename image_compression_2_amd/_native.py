@@ -23,6 +23,17 @@ F16_IEEE = 5   # out_dtype only: f16 output converted IEEE (overflow -> inf), th
 ACT_LINEAR, ACT_LRELU = 0, 1
 NHWC, NCHW, NHWC16 = 0, 1, 2
 
+
+def act_in_layout(layout):
+    """Flag for a conv entry point's `act`: the INPUT is stored in `layout` (ic2ops.h IC2_ACT_IN_LAYOUT)."""
+    return layout << 4
+
+
+def flr_out_layout(layout):
+    """Flag for ic2_flrelu_nhwc(16)'s `dtype_out`: the OUTPUT is stored in `layout` (ic2ops.h IC2_FLR_OUT_LAYOUT)."""
+    return layout << 4
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _I64 = ctypes.c_int64
@@ -33,6 +44,7 @@ _SIGS = {
     "ic2_abi_version": [],
     "ic2_dev_mode": [],
     "ic2_conv_plan": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I],
+    "ic2_conv_accepts_nhwc16": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I],
     "ic2_quantize_uniform": [_P, _I64, _I, _P, _P, _P],
     "ic2_quantize_codebook_argmin": [_P, _I64, _P, _I, _P, _P, _P, _P],
     "ic2_codebook_lookup": [_P, _I64, _P, _I, _P, _P, _P],
@@ -167,6 +179,13 @@ def conv_plan(dtype, out_dtype, out_layout, n, h, w, cin_p, cout_p, cout_valid, 
     """Name of the kernel instance(s) ic2_conv_igemm_ws launches for this geometry (the library's launch plan)."""
     return query("ic2_conv_plan", dtype, out_dtype, out_layout, n, h, w, cin_p, cout_p, cout_valid, kh, kw,
                  pad).decode()
+
+
+def conv_accepts_nhwc16(dtype, out_dtype, out_layout, n, h, w, cin_p, cout_p, cout_valid, kh, kw, pad):
+    """True when the conv the synthesis runs for this geometry (ic2_conv_wino where preferred, else ic2_conv_igemm_ws's
+    plan) reads channel-blocked input and the hand-off is kept for its kernel family (ic2_conv_accepts_nhwc16)."""
+    return bool(query("ic2_conv_accepts_nhwc16", dtype, out_dtype, out_layout, n, h, w, cin_p, cout_p, cout_valid, kh,
+                      kw, pad))
 
 
 def conv_igemm(x, w, y, dtype, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, ho, wo, oscale, bias,

@@ -53,6 +53,12 @@ struct IgemmArgs {
   // while the GEMM's K runs over [hi | hi | lo] against [hi | lo | hi] weights); x_hb32 = 32-channel blocks of the hi
   // part (0: plain storage).  K block b of 32 channels reads stored block ig_xb32(a, b): b, or b - x_hb32 past hi
   int x_pix, x_hb32;
+  // input layout, read by the halo-staging kernels (hg4, Winograd) and ToRGB only; the other kernels take NHWC and the
+  // entry points refuse blocked input for them.  x_img = stored elements per sample; x_plane = bytes from channels
+  // 0-15 to channels 16-31 of a pixel's 32-channel K block, K block b starting at byte 2 * x_plane * b.  NHWC:
+  // x_pix * h * w and 32.  Channel-blocked NHWC16 [n][cin_p / 16][h][w][16]: x_pix = 16, x_img = cin_p * h * w,
+  // x_plane = h * w * 32 (one 16-channel plane)
+  int x_img, x_plane;
   // Winograd F(2,3)-along-x kernel (wino.hip) only: output tile = wx_th rows x wx_twp pixel pairs, each row
   // served by wx_ns 16-lane pair blocks; halo line pitch wx_hp (64-B LDS rows per (halo row, column parity) line),
   // wx_nh halo rows used, wx_tx x wx_ty tiles per image
@@ -62,6 +68,17 @@ struct IgemmArgs {
   int out_ieee;
 };
 __device__ __forceinline__ int ig_xb32(const IgemmArgs& a, int b) { return b >= a.x_hb32 ? b - a.x_hb32 : b; }
+// Byte offset, from the first K block of sample 0, of 16-B chunk `chunk` (0..3: 8 channels each) of the 32-channel K
+// block of input pixel (nn, iy, ix), for the halo DMAs (< 2^31: the launchers bound the input's bytes)
+__device__ __forceinline__ uint32_t ig_halo_off(const IgemmArgs& a, int nn, int iy, int ix, int chunk) {
+  return (uint32_t)((nn * a.x_img + (iy * a.w_ + ix) * a.x_pix) * 2 + (chunk >> 1) * a.x_plane + (chunk & 1) * 16);
+}
+// input layout of a launch: plain NHWC storage of x_pix elements per pixel, or channel-blocked NHWC16
+inline void ig_set_input_layout(IgemmArgs& a, bool blocked) {
+  if (blocked) a.x_pix = 16;
+  a.x_img = blocked ? a.cin_p * a.h * a.w_ : a.x_pix * a.h * a.w_;
+  a.x_plane = blocked ? a.h * a.w_ * 32 : 32;
+}
 
 // Per-channel epilogue operands.  The epilogues load them for all their channel blocks BEFORE the first store: a
 // load placed after a store to y may alias it, so loading inside the store loop serialised one load round trip per

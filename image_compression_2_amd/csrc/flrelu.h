@@ -19,6 +19,7 @@ struct FlrArgs {
   int tiles_x, tiles_y, cblocks, nimg;
   int order;  // wide MFMA kernel: tile order, 0 = channel block fastest, 1 = x, y fastest (one plane per XCD run)
   int out_f16;  // MFMA kernels: output f16 (saturated) instead of bf16 (the synthesis's f16 mode)
+  int out_blocked;  // strip MFMA kernel: output channel-blocked NHWC16 [n][c_p/16][out_h][out_w][16] instead of NHWC
   float slope, lim;  // lrelu slope (<= 1) and clamp bound / gain (+inf = no clamp)
   float gdg[12];     // down taps * gain (horizontal pass, right after the activation)
   float gu[24];  // flipped (unless flip_filter) and scaled by `up` (sqrt of the up^2 gain per pass)
@@ -33,7 +34,8 @@ struct FlrArgs {
 // the MFMA kernels' f16 FIR taps (flrelu.hip; shared with the MFMA backward, flrelu_bwd.hip)
 void f16_round_taps(const float* exact, float* out, int n, int stride_groups);
 
-// NHWC or channel-blocked NHWC16 (strides in a), f16 (in_f16) or bf16 input, bf16 or f16 (a.out_f16) output, up in {2, 4} with 6*up taps, down 2 with 12 taps, no
+// NHWC or channel-blocked NHWC16 (strides in a), f16 (in_f16) or bf16 input, bf16 or f16 (a.out_f16) output, NHWC or
+// (a.out_blocked: f16 input on the strip kernel only) NHWC16, up in {2, 4} with 6*up taps, down 2 with 12 taps, no
 // bias (folded into the producer).  Sets tiles/cblocks itself.  Returns IC2_E_UNSUPPORTED when the
 // configuration has no MFMA instance.
 int flrelu_mfma_launch(FlrArgs a, int in_f16, int up, int down, int tu, int td, int delta, int n, hipStream_t s);

@@ -348,6 +348,12 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
                          float gain, float slope, float clamp, int flip, const float* post_scale, void* stream,
                          const char* name, bool in_blocked = false) {
   IC2_CHECK_ARG(x && y, "%s: null pointer", name);
+  // the output layout rides in the bits above the output dtype (ic2ops.h IC2_FLR_OUT_LAYOUT)
+  const int out_layout = IC2_FLR_OUT_LAYOUT_OF(dtype_out);
+  dtype_out = IC2_FLR_DTYPE_OF(dtype_out);
+  IC2_CHECK_ARG(out_layout == IC2_LAYOUT_NHWC || (out_layout == IC2_LAYOUT_NHWC16 && chlast),
+                "%s: output layout %d (NHWC, or NHWC16 from the NHWC / NHWC16 entry points)", name, out_layout);
+  const bool out_blocked = out_layout == IC2_LAYOUT_NHWC16;
   IC2_CHECK_ARG(n > 0 && c > 0 && in_h > 0 && in_w > 0 && up >= 1 && down >= 1, "%s: bad geometry", name);
   IC2_CHECK_ARG(fu_taps >= 1 && fd_taps >= 1 && fu_taps <= 24 && fd_taps <= 12, "%s: unsupported taps", name);
   const int ew = (in_w * up + (px0 + px1) - (fu_taps - 1) - (fd_taps - 1) + (down - 1)) / down;
@@ -392,6 +398,7 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
   const bool mfma_ok = chlast && (dtype_in == IC2_BF16 || dtype_in == IC2_F16) &&
                        (dtype_out == IC2_BF16 || dtype_out == IC2_F16) && b == nullptr && dx == dy;
   a.out_f16 = dtype_out == IC2_F16;
+  a.out_blocked = out_blocked;
   if ((use_mfma || dtype_in == IC2_F16) && mfma_ok) {
     float gu[24] = {}, gd[12] = {}, gdg[12] = {};
     for (int t = 0; t < fu_taps; ++t) gu[t] = (fu ? (flip ? fu[t] : fu[fu_taps - 1 - t]) : 1.f) * (float)up;
@@ -417,6 +424,11 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
       IC2_CHECK_LAUNCH(name);
       return IC2_OK;
     }
+  }
+  if (out_blocked) {
+    set_error("%s: channel-blocked output needs the strip MFMA instance (f16 input, bf16/f16 out, no bias, up 2/4 with "
+              "6*up taps, down 2 / 12 taps)", name);
+    return IC2_E_UNSUPPORTED;
   }
   if (in_blocked) {
     set_error("%s: channel-blocked input needs the MFMA instance (f16/bf16 in, bf16/f16 out, no bias, up 2/4 with 6*up "

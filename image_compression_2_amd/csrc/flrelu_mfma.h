@@ -12,6 +12,7 @@ typedef short fm_s4 __attribute__((ext_vector_type(4)));
 typedef float fm_f4 __attribute__((ext_vector_type(4)));
 typedef float fm_f2 __attribute__((ext_vector_type(2)));
 typedef uint32_t v2u32_t __attribute__((ext_vector_type(2)));
+typedef uint32_t v4u32_t __attribute__((ext_vector_type(4)));
 
 constexpr int FM_TAPS = 276;
 // the wide / strip kernels' table also holds the clamp-split horizontal taps: guh at [328, 352), gdgl at [428, 440)

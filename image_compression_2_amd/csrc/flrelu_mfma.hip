@@ -786,6 +786,32 @@ struct FmGeom3 {
   static_assert((NG - 1) * GRP_DW + (S - 1) * IN_PITCH + 8 * 8 * ((NINX + 7) / 8) <= RING_DW, "ring bounds");
 };
 
+// 4 x 4 transpose of 8-byte elements over a lane quad: on return lane p of a quad holds in v[i] what lane i held in
+// v[p].  Two butterfly stages (quad_perm xor 1, xor 2); in each, a lane sends the element its partner keeps the slot
+// of and receives into the slot it gives up.
+__device__ __forceinline__ void fm_quad_transpose(uint2 (&v)[4], int p) {
+  const bool b0 = (p & 1) != 0, b1 = (p & 2) != 0;
+  auto swap = [](uint32_t& lo, uint32_t& hi, bool up, auto ctrl) {
+    constexpr int CTRL = decltype(ctrl)::value;
+    const uint32_t send = up ? lo : hi;
+    const uint32_t recv = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, CTRL, 0xf, 0xf, true);
+    lo = up ? recv : lo;
+    hi = up ? hi : recv;
+  };
+  using X1 = std::integral_constant<int, 0xB1>;  // quad_perm [1, 0, 3, 2]
+  using X2 = std::integral_constant<int, 0x4E>;  // quad_perm [2, 3, 0, 1]
+#pragma unroll
+  for (int i = 0; i < 4; i += 2) {
+    swap(v[i].x, v[i + 1].x, b0, X1{});
+    swap(v[i].y, v[i + 1].y, b0, X1{});
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    swap(v[i].x, v[i + 2].x, b1, X2{});
+    swap(v[i].y, v[i + 2].y, b1, X2{});
+  }
+}
+
 // diagnostic builds only (tools/build_abl.sh, wrong results): IC2_FM3_ABL bit 0 skips the ring waits, bit 1 the ring
 // DMAs, bit 2 the horizontal pass, bit 3 the vertical up, bit 4 the vertical down, bit 5 the two in-block barriers,
 // bit 6 the output stores (issued to the dropped offset: same instructions, no bytes)
@@ -801,9 +827,19 @@ struct FmGeom3 {
 #ifndef FM3_DEFER_ST
 #define FM3_DEFER_ST 0
 #endif
-template <int U, int DELTA, int NW, bool CL>
+// BLK: channel-blocked NHWC16 output [n][c_p/16][out_h][out_w][16] (the hand-off to a conv that reads it blocked).  A
+// wave then owns the 4 adjacent output columns 4 wave .. 4 wave + 3 (instead of wave + NW i) and transposes the 4
+// columns x 4 rows held by each lane quad before the store, so the 16 lanes (4 columns x 4 channel quads) of one row
+// fill one 128-B line and every store instruction of an interior tile writes 4 whole lines.
+// the blocked output stored 16 B per lane, 2 instructions per tile (1), or 8 B per lane, 4 instructions (0)
+#ifndef FM3_BLK16
+#define FM3_BLK16 1
+#endif
+template <int U, int DELTA, int NW, bool CL, bool BLK>
 __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs a, int nitems, int nseg, int seg_len) {
   constexpr int TOX = 32, NT = 64 * NW, RR = 16 / NW, OCW = TOX / NW;
+  // output store instructions per wave per tile, exact and known here: the vmcnt waits below count them
+  constexpr int NST = BLK && FM3_BLK16 ? OCW / 2 : OCW;
   using G2 = FmGeom2<U, TOX>;
   using G = FmGeom3<U>;
   constexpr int NINX = G::NINX, NBX = G2::NBX, NOB = G2::NOB, S = G::S, NG = G::NG;
@@ -956,23 +992,62 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
     item_geom(w, n, ox0, c0, t0, nt);
     const int iy0 = (32 * t0 + DELTA - a.py0) / U, sx0 = (ox0 * 2 - a.px0 + DELTA) / U;
     const bool has_next = w + (int)gridDim.x < nitems;
-    // this wave's DMA of the item's first rows; the previous item's last OCW output stores (issued after that
-    // DMA, always exactly OCW) stay in flight
+    // this wave's DMA of the item's first rows; the previous item's last NST output stores (issued after that
+    // DMA, always exactly NST) stay in flight
     if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OCW) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
     first = false;
     __syncthreads();
     float4 psv = make_float4(1.f, 1.f, 1.f, 1.f);
     if (a.post_scale) psv = *reinterpret_cast<const float4*>(ps_lds + 4 * g);
     const float ps[4] = {psv.x, psv.y, psv.z, psv.w};
+    // the sample's image, at this item's channels: 16 of every pixel's c_p (NHWC) or its own plane (BLK)
     const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(yout + (int64_t)n * a.out_h * a.out_w * a.c_p + c0), 0, FM_OOB, 0x00020000);
+        (void*)(yout + (int64_t)n * a.out_h * a.out_w * a.c_p + (BLK ? (int64_t)c0 * a.out_h * a.out_w : (int64_t)c0)), 0,
+        FM_OOB, 0x00020000);
     const int kend = 2 * nt;  // blocks 0 .. kend
 
     fm_f4 acc_a[OCW], acc_b[OCW];
     // store tile t0 + tt from acc_a: lane (g, oy = li) holds channels c0 + 4g .. +3 of output pixel (oy, ox); exactly
-    // OCW buffer stores per wave (out-of-range pixels at the dropped offset FM_OOB)
+    // NST buffer stores per wave (out-of-range pixels at the dropped offset FM_OOB)
     auto store_tile = [&](int tt) __attribute__((always_inline)) {
+      if constexpr (BLK) {
+        // lane (g, li = 4 tq + tp) holds row li of columns 4 wave + i; after the quad transpose it holds column
+        // 4 wave + tp of rows 4 tq + i: store i covers rows i, 4 + i, 8 + i, 12 + i, each one 128-B line of 4 pixels x
+        // 32 B.  Exactly NST stores per wave (the vmcnt counts below)
+        static_assert(OCW == 4, "quad transpose: 4 columns per wave");
+        uint2 v[OCW];
+#pragma unroll
+        for (int i = 0; i < OCW; ++i)
+          v[i] = fm_out4(a.out_f16, acc_a[i][0] * ps[0], acc_a[i][1] * ps[1], acc_a[i][2] * ps[2], acc_a[i][3] * ps[3]);
+        fm_quad_transpose(v, tp);
+        const int gy0 = 16 * (t0 + tt) + 4 * tq, gx = ox0 + 4 * wave + tp;
+        if constexpr (FM3_BLK16) {
+          // 16 B per lane: stores 2 h and 2 h + 1 trade halves across 16-lane rows (v_permlane16_swap: the odd rows of
+          // its first operand with the even rows of its second), so the lanes of an even channel quad g hold channels
+          // 4 g .. 4 g + 7 of store 2 h's pixel and those of an odd g channels 4 g - 4 .. 4 g + 3 of store 2 h + 1's:
+          // one instruction writes 8 whole lines, NST = 2 instructions per wave per tile
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const auto x = __builtin_amdgcn_permlane16_swap(v[2 * h].x, v[2 * h + 1].x, false, false);
+            const auto y = __builtin_amdgcn_permlane16_swap(v[2 * h].y, v[2 * h + 1].y, false, false);
+            const int gy = gy0 + 2 * h + (g & 1);
+            const uint32_t off =
+                (gy < a.out_h && gx < a.out_w) ? (uint32_t)((gy * a.out_w + gx) * 32 + 16 * (g >> 1)) : FM_OOB;
+            const v4u32_t q = {x[0], y[0], x[1], y[1]};
+            __builtin_amdgcn_raw_buffer_store_b128(q, ors, (IC2_FM3_ABL & 64) ? FM_OOB : off, 0, 0);
+          }
+          return;
+        }
+#pragma unroll
+        for (int i = 0; i < OCW; ++i) {
+          const int gy = gy0 + i;
+          const uint32_t off = (gy < a.out_h && gx < a.out_w) ? (uint32_t)((gy * a.out_w + gx) * 32 + 8 * g) : FM_OOB;
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, v[i]), ors, (IC2_FM3_ABL & 64) ? FM_OOB : off,
+                                                0, 0);
+        }
+        return;
+      }
       const int gy = 16 * (t0 + tt) + li;
 #pragma unroll
       for (int i = 0; i < OCW; ++i) {
@@ -1079,29 +1154,31 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
       // the ring group this block's DMA (issued at block k-1's barrier below) filled must have landed before
       // block k+1's vertical up: wait for it behind the stores of the tile finished at block k-1 (odd k >= 3)
       if (!(IC2_FM3_ABL & 1) && k >= 1 && k < kend) {
-        // block k-1's ring DMA must have landed (block k+1 reads it); younger: the stores of a tile (exactly OCW) --
+        // block k-1's ring DMA must have landed (block k+1 reads it); younger: the stores of a tile (exactly NST) --
         // deferred: issued in this block (odd k >= 3) or in block k-1 after its DMA (even k >= 4); else issued at the
         // end of block k-1 (odd k >= 3) -- and, issued early, this block's own DMA (this wave's share, uniform)
         const bool st = (MODE == 1 && k >= 3) || (FM3_DEFER_ST && MODE == 2 && k >= 4);
         const int nd = FM3_EARLY && dma ? my_dma : 0;
         if (nd == 0) {
-          if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OCW) : "memory");
+          if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
           else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else if (nd == 1) {
-          if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OCW + 1) : "memory");
+          if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST + 1) : "memory");
           else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
         } else {
-          if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OCW + 2) : "memory");
+          if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST + 2) : "memory");
           else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         }
       }
       if constexpr (!(IC2_FM3_ABL & 32)) __syncthreads();  // D complete; every wave's horizontal reads of V are done
       if (!FM3_EARLY && dma) load_group(n, iy0, sx0, c0, k + U + 1);  // rows of block k+2
       if constexpr (!(IC2_FM3_ABL & 16)) {
+        // output column of accumulator i: wave + NW i, or 4 wave + i (BLK).  Either way one read instruction takes one
+        // column, so its lanes differ only in (row 4 g + tq, quad tp): the bank pattern D_PITCH was chosen for
         fm_s4 da[OCW];
 #pragma unroll
         for (int i = 0; i < OCW; ++i)
-          da[i] = fm_tr_read(d_img + (4 * g + tq) * G2::D_PITCH + (wave + NW * i) * G2::D_XP + 2 * tp);
+          da[i] = fm_tr_read(d_img + (4 * g + tq) * G2::D_PITCH + (BLK ? 4 * wave + i : wave + NW * i) * G2::D_XP + 2 * tp);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (MODE == 0) {
 #pragma unroll
@@ -1136,7 +1213,7 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
   }
 }
 
-template <int U, int DELTA, bool CL>
+template <int U, int DELTA, bool CL, bool BLK>
 static void fm3_launch_cl(FlrArgs a, int n, hipStream_t s) {
   constexpr int TOX = 32, NW = 8;
   a.tiles_x = (int)ceil_div(a.out_w, TOX);
@@ -1147,7 +1224,7 @@ static void fm3_launch_cl(FlrArgs a, int n, hipStream_t s) {
     int dev = 0, cus = 0, per_cu = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, flrelu_mfma3_kernel<U, DELTA, NW, CL>, 64 * NW, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, flrelu_mfma3_kernel<U, DELTA, NW, CL, BLK>, 64 * NW, 0);
     resident = (cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 1);
   }
   // strip segmentation: fm_strip_segments (flrelu_mfma.h); knob IC2_FLR_SEGS=0 keeps the round-3 rule
@@ -1158,7 +1235,7 @@ static void fm3_launch_cl(FlrArgs a, int n, hipStream_t s) {
   nseg = (int)ceil_div(a.tiles_y, seg_len);
   const int nitems = (int)(nstrips * nseg);
   const int grid = nitems < resident ? nitems : resident;
-  hipLaunchKernelGGL((flrelu_mfma3_kernel<U, DELTA, NW, CL>), dim3((unsigned)grid), dim3(64 * NW), 0, s, a, nitems,
+  hipLaunchKernelGGL((flrelu_mfma3_kernel<U, DELTA, NW, CL, BLK>), dim3((unsigned)grid), dim3(64 * NW), 0, s, a, nitems,
                      nseg, seg_len);
 }
 
@@ -1188,19 +1265,24 @@ static void fm2_launch_cl(FlrArgs a, int n, hipStream_t s) {
 // (lim in [2^-4, 2^12]: SG3's conv_clamp 256 / sqrt(2)); knob IC2_FLR_CLSPLIT=0 keeps the 3-instruction activation.
 // (The kernel's ABL template parameter held the round-2 ablation builds; only ABL = 0 is instantiated.)
 template <int U, int DELTA>
-static void fm2_launch(FlrArgs a, int n, hipStream_t s) {
+static int fm2_launch(FlrArgs a, int n, hipStream_t s) {
   static const bool split = knob("IC2_FLR_CLSPLIT", 1) != 0;
   // knob IC2_FLR_STRIP=0: the round-2 tile kernel instead of the strip-streaming one
   static const bool strip = knob("IC2_FLR_STRIP", 1) != 0;
   const bool cl = split && a.lim >= 0.0625f && a.lim <= 4096.f;
-  if (strip) {
-    if (cl) fm3_launch_cl<U, DELTA, true>(a, n, s);
-    else fm3_launch_cl<U, DELTA, false>(a, n, s);
+  if (a.out_blocked) {  // only the strip kernel writes the channel-blocked output
+    if (!strip) return IC2_E_UNSUPPORTED;
+    if (cl) fm3_launch_cl<U, DELTA, true, true>(a, n, s);
+    else fm3_launch_cl<U, DELTA, false, true>(a, n, s);
+  } else if (strip) {
+    if (cl) fm3_launch_cl<U, DELTA, true, false>(a, n, s);
+    else fm3_launch_cl<U, DELTA, false, false>(a, n, s);
   } else if (cl) {
     fm2_launch_cl<U, DELTA, true, 0>(a, n, s);
   } else {
     fm2_launch_cl<U, DELTA, false, 0>(a, n, s);
   }
+  return IC2_OK;
 }
 
 template <int U, int DELTA, bool IN_F16, bool ALIAS, int NW>
@@ -1257,19 +1339,15 @@ int flrelu_mfma_launch(FlrArgs a, int in_f16, int up, int down, int tu, int td, 
   static const bool wide_all = knob("IC2_FLR_WIDE_ALL", 1) != 0;
   if (in_f16 && wide && (wide_all || ceil_div(a.out_w, 32) * 32 <= ceil_div(a.out_w, 16) * 16) &&
       (int64_t)n * ceil_div(a.out_h, 16) * ceil_div(a.out_w, 32) * (a.c_p / 16) < (1LL << 31)) {
-    if (up == 2) {
-      if (delta == 0) fm2_launch<2, 0>(a, n, s);
-      else fm2_launch<2, 1>(a, n, s);
-    } else {
-      switch (delta) {
-        case 0: fm2_launch<4, 0>(a, n, s); break;
-        case 1: fm2_launch<4, 1>(a, n, s); break;
-        case 2: fm2_launch<4, 2>(a, n, s); break;
-        default: fm2_launch<4, 3>(a, n, s); break;
-      }
+    if (up == 2) return delta == 0 ? fm2_launch<2, 0>(a, n, s) : fm2_launch<2, 1>(a, n, s);
+    switch (delta) {
+      case 0: return fm2_launch<4, 0>(a, n, s);
+      case 1: return fm2_launch<4, 1>(a, n, s);
+      case 2: return fm2_launch<4, 2>(a, n, s);
+      default: return fm2_launch<4, 3>(a, n, s);
     }
-    return IC2_OK;
   }
+  if (a.out_blocked) return IC2_E_UNSUPPORTED;  // the tile kernels below write NHWC only
   a.tiles_x = (int)ceil_div(a.out_w, 16);
   a.tiles_y = (int)ceil_div(a.out_h, 16);
   a.cblocks = a.c_p / 16;

@@ -694,9 +694,9 @@ __device__ __forceinline__ void hg4_body(const IgemmArgs& a, int tiles_x, int ti
     const int hy = hp / G::HW, hx = hp - (hp / G::HW) * G::HW;
     const int iy = oy0 - a.pad + hy, ix = ox0 - a.pad + hx;
     const bool ok = g < G::NHI && hp < G::NH && (unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w_;
-    h_off[k] = ok ? (uint32_t)((((nn * a.h + iy) * a.w_ + ix) * a.x_pix + ((pch ^ (((hp >> 2) & 1) << 1)) << 3)) * 2)
-                  : kOob;
+    h_off[k] = ok ? ig_halo_off(a, nn, iy, ix, pch ^ (((hp >> 2) & 1) << 1)) : kOob;
   }
+  const int x_cb = 2 * a.x_plane;  // bytes from one stored 32-channel block of the input to the next (64 in NHWC)
   int brow[J];
 #pragma unroll
   for (int j = 0; j < J; ++j) {
@@ -737,7 +737,7 @@ __device__ __forceinline__ void hg4_body(const IgemmArgs& a, int tiles_x, int ti
   };
   auto issue_hb = [&](int cb) {  // HB: all HPW DMAs of this wave for the halo of block cb -> halo cb & 1 (or dummy)
     const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(xg + (int64_t)ig_xb32(a, cb) * 64), 0, kOob, kRsrcWord3);
+        __builtin_amdgcn_make_buffer_rsrc((void*)(xg + (int64_t)ig_xb32(a, cb) * x_cb), 0, kOob, kRsrcWord3);
 #pragma unroll
     for (int k = 0; k < HPW; ++k) {
       char* dst = wid + 4 * k < G::NHI ? hal + (cb & 1) * G::HALO_B + (wid + 4 * k) * 1024 : hal + 2 * G::HALO_B;
@@ -746,7 +746,7 @@ __device__ __forceinline__ void hg4_body(const IgemmArgs& a, int tiles_x, int ti
   };
   auto issue_h1 = [&](int cb, int k) {  // DMA k of this wave for the halo of block cb -> halo cb & 1
     const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(xg + (int64_t)ig_xb32(a, cb) * 64), 0, kOob, kRsrcWord3);
+        __builtin_amdgcn_make_buffer_rsrc((void*)(xg + (int64_t)ig_xb32(a, cb) * x_cb), 0, kOob, kRsrcWord3);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(
         rs, (__attribute__((address_space(3))) void*)(hal + (cb & 1) * G::HALO_B + (wid + 4 * k) * 1024), 16, h_off[k],
         0, 0, 0);
@@ -1476,7 +1476,10 @@ __global__ void __launch_bounds__(256) torgb_kernel(IgemmArgs a) {
   float* yo = reinterpret_cast<float*>(a.y);
   const int stride = gridDim.x * (256 / L);
   for (int p = tid / L; p < a.M; p += stride) {
-    const uint4* src = reinterpret_cast<const uint4*>(xg + (int64_t)p * a.cin_p + sub * 16);
+    // the lane's 16 channels of pixel p: 32 B of the pixel (NHWC) or of plane `sub` of the pixel's sample (blocked)
+    const uint4* src = reinterpret_cast<const uint4*>(
+        a.x_pix == 16 ? xg + (int64_t)(p / hw) * a.x_img + ((int64_t)sub * hw + p % hw) * 16
+                               : xg + (int64_t)p * a.cin_p + sub * 16);
     const uint4 u0 = src[0], u1 = src[1];
     const uint32_t w32[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
     float acc[CV];
@@ -1649,6 +1652,12 @@ static const char* conv_choice_name(const ConvChoice& c, int dtype, int n, int h
   return buf;
 }
 
+// the kernels of this file whose input addressing covers the channel-blocked layout (IgemmArgs::x_plane): the hg4
+// halo staging and ToRGB, on plain 2-byte operands (the split inputs have their own storage)
+static bool conv_kind_reads_blocked(ConvKind kind, int dtype) {
+  return (kind == CK_HG4 || kind == CK_TORGB) && (dtype == IC2_BF16 || dtype == IC2_F16);
+}
+
 // Images per launch: the buffer-descriptor kernels (8-phase, hg4) address < 2^31 bytes per operand, so a batch whose
 // input exceeds that runs in chunks of whole images (each chunk with its own launch plan) instead of falling back to
 // the generic tile (SG3-T-1024 / the 1024^2 encoder at batch 8: 1024^2 x 192 x 2 B = 403 MB per image).
@@ -1677,6 +1686,22 @@ extern "C" const char* ic2_conv_plan(int dtype, int out_dtype, int out_layout, i
   return f16_name;
 }
 
+// The filtered lrelu -> conv hand-off stays channel-blocked where the consumer reads it that way and does not lose
+// more than the filtered lrelu gains (per kernel family, profiles/r7_act_blocked_ab.txt); knobs IC2_ACT_BLOCKED_WINO /
+// _HG4 / _TORGB = 0 / 1 (IC2_DEV=1) override the family defaults below
+extern "C" int ic2_conv_accepts_nhwc16(int dtype, int out_dtype, int out_layout, int n, int h, int w_, int cin_p,
+                                       int cout_p, int cout_valid, int kh, int kw, int pad) {
+  static const bool on_wino = knob("IC2_ACT_BLOCKED_WINO", 1) != 0, on_hg4 = knob("IC2_ACT_BLOCKED_HG4", 1) != 0,
+                    on_torgb = knob("IC2_ACT_BLOCKED_TORGB", 0) != 0;  // ToRGB +20 us vs its filtered lrelu's -19 us
+  const int ho = h + 2 * pad - kh + 1, wo = w_ + 2 * pad - kw + 1;
+  if (n <= 0 || ho <= 0 || wo <= 0 || cin_p <= 0 || cin_p % 32 || cout_p <= 0 || cout_p % 32) return 0;
+  if (ic2_conv_wino_preferred(dtype, n, h, w_, cin_p, cout_p, kh, kw, pad)) return on_wino;
+  const int nc = conv_chunk_n(dtype, n, h, w_, cin_p);
+  const ConvChoice c = conv_choice(dtype, out_layout, out_dtype, nc, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad);
+  if (!conv_kind_reads_blocked(c.kind, dtype)) return 0;
+  return c.kind == CK_HG4 ? on_hg4 : on_torgb;
+}
+
 extern "C" int64_t ic2_conv_igemm_ws_bytes(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw,
                                            int pad) {
   const int ho = h + 2 * pad - kh + 1, wo = w_ + 2 * pad - kw + 1;
@@ -1693,6 +1718,12 @@ extern "C" int ic2_conv_igemm_ws(const void* x, const void* w, void* y, int dtyp
                                  float clamp, float out_mul, int out_layout, void* workspace, int64_t ws_bytes,
                                  void* stream) {
   IC2_CHECK_ARG(x && w && y, "conv_igemm: null pointer");
+  // the input layout rides in the bits above the activation (ic2ops.h IC2_ACT_IN_LAYOUT)
+  const int act_flags = act, in_layout = IC2_ACT_IN_LAYOUT_OF(act_flags);
+  act = IC2_ACT_OF(act_flags);
+  IC2_CHECK_ARG(in_layout == IC2_LAYOUT_NHWC || in_layout == IC2_LAYOUT_NHWC16, "conv_igemm: bad input layout %d",
+                in_layout);
+  const bool in_blocked = in_layout == IC2_LAYOUT_NHWC16;
   IC2_CHECK_ARG(dtype == IC2_F32 || dtype == IC2_BF16 || dtype == IC2_F16 || dtype == IC2_BF16X3 || dtype == IC2_F16X2,
                 "conv_igemm: bad dtype %d", dtype);
   IC2_CHECK_ARG(dtype != IC2_BF16X3 || (cin_p % 96 == 0 && out_layout == IC2_LAYOUT_NHWC),
@@ -1722,8 +1753,8 @@ extern "C" int ic2_conv_igemm_ws(const void* x, const void* w, void* y, int dtyp
       const int rc = ic2_conv_igemm_ws(reinterpret_cast<const char*>(x) + n0 * x_img, w,
                                        reinterpret_cast<char*>(y) + n0 * y_img, dtype, out_dtype, nn, h, w_, cin_p,
                                        cout_p, cout_valid, kh, kw, pad, ho, wo,
-                                       oscale ? oscale + (int64_t)n0 * cout_p : nullptr, bias, act, slope, act_gain,
-                                       clamp, out_mul, out_layout, workspace, ws_bytes, stream);
+                                       oscale ? oscale + (int64_t)n0 * cout_p : nullptr, bias, act_flags, slope,
+                                       act_gain, clamp, out_mul, out_layout, workspace, ws_bytes, stream);
       if (rc != IC2_OK) return rc;
     }
     return IC2_OK;
@@ -1743,6 +1774,7 @@ extern "C" int ic2_conv_igemm_ws(const void* x, const void* w, void* y, int dtyp
   a.in_gn = nullptr; a.in_slope = 0.f;
   a.x_pix = x_pix_of(dtype, cin_p);
   a.x_hb32 = x_hb32_of(dtype, cin_p);
+  ig_set_input_layout(a, in_blocked);
   const int kdt = dtype == IC2_BF16X3 ? IC2_BF16 : dtype == IC2_F16X2 ? IC2_F16 : dtype;  // the kernels' operand type
   static const int group = [] {
     const int g = knob("IC2_IGEMM_GROUP", 1);  // 1 = o-tiles of a p-tile side by side (measured best)
@@ -1755,6 +1787,10 @@ extern "C" int ic2_conv_igemm_ws(const void* x, const void* w, void* y, int dtyp
   a.o_base = 0;
   hipStream_t s = as_stream(stream);
   ConvChoice c = conv_choice(dtype, out_layout, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad);
+  IC2_CHECK_ARG(!in_blocked || conv_kind_reads_blocked(c.kind, dtype),
+                "conv_igemm: channel-blocked (NHWC16) input is read by the hg4 halo kernels and ToRGB only, with plain "
+                "bf16 / f16 operands; this geometry runs as %s (ic2_conv_accepts_nhwc16 says which do)",
+                conv_choice_name(c, dtype, n, ho, wo, cin_p, cout_p));
   dtype = kdt;
   IgPlan& pl = c.pl;
   if (pl.splits > 1 && (workspace == nullptr || ws_bytes < (int64_t)pl.splits * M * cout_p * 4)) pl.splits = 1;
@@ -1879,6 +1915,7 @@ int conv_gn_fused(const void* x, const void* w, void* y, int dtype, int n, int h
     a.in_gn = nullptr; a.in_slope = 0.f;
     a.x_pix = x_pix_of(dtype, cin_p);
     a.x_hb32 = x_hb32_of(dtype, cin_p);
+    ig_set_input_layout(a, false);
     const bool f16 = dtype == IC2_F16X2;
     const int nc = conv_chunk_n(dtype, n, h, w_, cin_p);
     const int64_t ntile = ceil_div(wo, 32) * ceil_div(ho, x3_gn_th(cout_p));
@@ -1929,6 +1966,7 @@ int conv_gn_fused(const void* x, const void* w, void* y, int dtype, int n, int h
   a.o_base = 0;
   a.in_gn = in_gn; a.in_slope = in_slope;
   a.x_pix = cin_p; a.x_hb32 = 0;
+  ig_set_input_layout(a, false);
   if (fuse) {
     if (cin_p == 32 && cout_p == 32) launch_hconv<32, 32, true>(a, s);
     else if (cin_p == 32) launch_hconv<32, 64, true>(a, s);

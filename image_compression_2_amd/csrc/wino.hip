@@ -140,8 +140,7 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
     const int line = l / hp, idx = l - line * hp;
     const int iy = oy0 - a.pad + (line >> 1), ix = 2 * px0 - a.pad + 2 * idx + (line & 1);
     const bool ok = l < a.wx_nh && (unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w_;
-    h_off[k] = ok ? (uint32_t)((((nn * a.h + iy) * a.w_ + ix) * a.cin_p + ((pch ^ (((idx >> 2) & 1) << 1)) << 3)) * 2)
-                  : kOob;
+    h_off[k] = ok ? ig_halo_off(a, nn, iy, ix, pch ^ (((idx >> 2) & 1) << 1)) : kOob;
   }
   // input-fragment offsets at ky = 0: pair block b = 2 pg + jb is 16 pairs of tile row b / ns; this half's 3 of the
   // pair's 4 pixels (half + m, m < 3: positions 0, 1 use pixels 0..2, positions 2, 3 pixels 1..3).  Lanes past the
@@ -161,6 +160,7 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
   const int ky_step = 2 * hp * 64;  // bytes per kernel row in the halo
   const int aoff = wx_off(fr, fh) + half * 2 * 64 * 64;
   const int CB = a.cin_p >> 5;
+  const int x_cb = 2 * a.x_plane;  // bytes from one 32-channel K block of the input to the next (64 in NHWC)
 
   // half-slab j (0..5) of block cb: kernel row j >> 1, channel half j & 1 -> ring slot j (size 0 past the end)
   auto issue_hs = [&](int cb, int j) {
@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
   };
   auto issue_hp = [&](int cb, int k) {  // DMA k of this wave for the halo of block cb -> halo cb & 1
     const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(xg + (int64_t)cb * 64), 0, cb < CB ? kOob : 0, kRsrcWord3);
+        __builtin_amdgcn_make_buffer_rsrc((void*)(xg + (int64_t)cb * x_cb), 0, cb < CB ? kOob : 0, kRsrcWord3);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(
         rs, (__attribute__((address_space(3))) void*)(hal + (cb & 1) * WX_HALO + (wid + WX_NW * k) * 1024), 16,
         h_off[k], 0, 0, 0);
@@ -562,6 +562,12 @@ extern "C" int ic2_conv_wino(const void* x, const void* u, void* y, int dtype, i
                              int out_layout, void* stream) {
   IC2_CHECK_ARG(x && u && y, "conv_wino: null pointer");
   IC2_CHECK_ARG(dtype == IC2_F16, "conv_wino: f16 operands only (dtype %d)", dtype);
+  // the input layout rides in the bits above the activation (ic2ops.h IC2_ACT_IN_LAYOUT)
+  const int act_flags = act, in_layout = IC2_ACT_IN_LAYOUT_OF(act_flags);
+  act = IC2_ACT_OF(act_flags);
+  IC2_CHECK_ARG(in_layout == IC2_LAYOUT_NHWC || in_layout == IC2_LAYOUT_NHWC16, "conv_wino: bad input layout %d",
+                in_layout);
+  const bool in_blocked = in_layout == IC2_LAYOUT_NHWC16;
   IC2_CHECK_ARG(out_dtype == IC2_F32 || out_dtype == IC2_BF16 ||
                     ((out_dtype == IC2_F16 || out_dtype == IC2_F16_IEEE) && out_layout != IC2_LAYOUT_NCHW),
                 "conv_wino: bad out dtype %d", out_dtype);
@@ -584,8 +590,8 @@ extern "C" int ic2_conv_wino(const void* x, const void* u, void* y, int dtype, i
       const int nn = n - n0 < nc ? n - n0 : nc;
       const int rc = ic2_conv_wino(reinterpret_cast<const char*>(x) + n0 * x_img, u,
                                    reinterpret_cast<char*>(y) + n0 * y_img, dtype, out_dtype, nn, h, w_, cin_p, cout_p,
-                                   cout_valid, pad, ho, wo, oscale ? oscale + (int64_t)n0 * cout_p : nullptr, bias, act,
-                                   slope, act_gain, clamp, out_mul, out_layout, stream);
+                                   cout_valid, pad, ho, wo, oscale ? oscale + (int64_t)n0 * cout_p : nullptr, bias,
+                                   act_flags, slope, act_gain, clamp, out_mul, out_layout, stream);
       if (rc != IC2_OK) return rc;
     }
     return IC2_OK;
@@ -612,6 +618,7 @@ extern "C" int ic2_conv_wino(const void* x, const void* u, void* y, int dtype, i
   a.out_layout = out_layout; a.out_dtype = out_dtype; a.out_ieee = out_ieee;
   a.gn_part = nullptr; a.gn_groups = 0; a.gn_c = 0; a.in_gn = nullptr; a.in_slope = 0.f;
   a.x_pix = cin_p; a.x_hb32 = 0;
+  ig_set_input_layout(a, in_blocked);
   a.wx_twp = t.twp; a.wx_th = t.th; a.wx_ns = t.ns; a.wx_hp = t.hp; a.wx_nh = t.nh; a.wx_tx = t.tx; a.wx_ty = t.ty;
   hipLaunchKernelGGL(wino_fx_f16_kernel, dim3((unsigned)t.blocks), dim3(64 * WX_NW), 0, as_stream(stream), a);
   IC2_CHECK_LAUNCH("conv_wino");

@@ -39,6 +39,9 @@ from . import sg3_ops
 # conv -> filtered lrelu hand-off in the channel-blocked NHWC16 layout (bf16 mode); knob IC2_FLR_BLOCKED=0 (IC2_DEV=1):
 # plain NHWC
 _FLR_BLOCKED = nv.knob("IC2_FLR_BLOCKED", 1) != 0
+# filtered lrelu -> conv hand-off channel-blocked too, on the no-grad 16-bit synthesis path, wherever the next layer's
+# conv kernel reads it that way (ic2_conv_accepts_nhwc16); False (knob IC2_ACT_BLOCKED=0 under IC2_DEV=1): plain NHWC
+_ACT_BLOCKED = nv.knob("IC2_ACT_BLOCKED", 1) != 0
 # longest row (w_dim, cin) of ic2_modconv_prep_batched's LDS-staged small GEMM (synth_ops.hip kSmK)
 _MOD_BATCH_MAX = 512
 
@@ -380,9 +383,30 @@ class SynthesisLayer(torch.nn.Module):
         return xs, os_
 
     # ---- NHWC pipeline step ------------------------------------------------------------------
-    def run_nhwc(self, x, n, dt, oscale, post_scale, final_scale=None):
-        """x: NHWC [n, in, in, cin_p] already scaled by this layer's xscale.  Returns NHWC output scaled by
-        post_scale (next layer's xscale), or -- for ToRGB -- the final NCHW f32 image * final_scale."""
+    def takes_blocked_input(self, n, dt):
+        """True when this layer's conv reads its input channel-blocked ([n, cin_p/16, in, in, 16]) on the no-grad
+        16-bit path: the library's predicate for the kernel the launch plan picks, under the module switch."""
+        if not _ACT_BLOCKED or dt not in (torch.bfloat16, torch.float16):
+            return False
+        s_in, k = int(self.in_size[0]), self.conv_kernel
+        if self.is_torgb:
+            out_dt, layout = nv.F32, nv.NCHW
+        else:
+            out_dt, layout = nv.F16, (nv.NHWC16 if _FLR_BLOCKED else nv.NHWC)
+        return nv.conv_accepts_nhwc16(nv.dtype_code(dt), out_dt, layout, n, s_in, s_in, self.cin_p, self.cout_p,
+                                      self.out_channels, k, k, k - 1)
+
+    def writes_blocked_output(self, dt):
+        """True when this layer's filtered lrelu has the strip MFMA instance that writes the channel-blocked layout
+        (f16 conv output, up 2 / 4 with 6 * up taps, down 2 with 12 taps)."""
+        return (not self.is_torgb and dt in (torch.bfloat16, torch.float16) and self.up_factor in (2, 4)
+                and self.down_factor == 2 and self._fu is not None and self._fd is not None
+                and self._fu.shape[0] == 6 * self.up_factor and self._fd.shape[0] == 12)
+
+    def run_nhwc(self, x, n, dt, oscale, post_scale, final_scale=None, x_blocked=False, out_blocked=False):
+        """x: NHWC [n, in, in, cin_p] (x_blocked: [n, cin_p/16, in, in, 16]) already scaled by this layer's xscale.
+        Returns NHWC (out_blocked: channel-blocked) output scaled by post_scale (next layer's xscale), or -- for
+        ToRGB -- the final NCHW f32 image * final_scale."""
         s_in = int(self.in_size[0])
         k = self.conv_kernel
         pad = k - 1
@@ -390,20 +414,22 @@ class SynthesisLayer(torch.nn.Module):
         wp, _, bp = self.packed(dt)
         stream = nv.stream_of(x)
         nv.note_flops(2 * n * conv * conv * self.out_channels * self.in_channels * k * k)
+        in_flag = nv.act_in_layout(nv.NHWC16) if x_blocked else 0  # the input layout rides above the conv's `act`
         if self.is_torgb:
             assert self.up_factor == 1 and self.down_factor == 1 and self.padding == [0, 0, 0, 0]
             out = torch.empty([n, self.out_channels, conv, conv], dtype=torch.float32, device=x.device)
             clamp = float(self.conv_clamp) if self.conv_clamp is not None else -1.0
             nv.conv_igemm(nv.ptr(x), nv.ptr(wp), nv.ptr(out), nv.dtype_code(dt), nv.F32, n, s_in, s_in, self.cin_p,
                           self.cout_p, self.out_channels, k, k, pad, conv, conv, nv.ptr(oscale), nv.ptr(bp),
-                          nv.ACT_LRELU, 1.0, 1.0, clamp, float(1.0 if final_scale is None else final_scale), nv.NCHW,
-                          stream, x.device)
+                          nv.ACT_LRELU | in_flag, 1.0, 1.0, clamp,
+                          float(1.0 if final_scale is None else final_scale), nv.NCHW, stream, x.device)
             return out
-        y, blocked = self.conv_nhwc(x, n, dt, oscale)
-        return self.flrelu_nhwc(y, dt, post_scale, blocked=blocked)
+        y, blocked = self.conv_nhwc(x, n, dt, oscale, x_blocked=x_blocked)
+        return self.flrelu_nhwc(y, dt, post_scale, blocked=blocked, out_blocked=out_blocked)
 
-    def conv_nhwc(self, x, n, dt, oscale):
-        """The modulated conv of a non-ToRGB layer: -> (conv output y, blocked layout?) for flrelu_nhwc."""
+    def conv_nhwc(self, x, n, dt, oscale, x_blocked=False):
+        """The modulated conv of a non-ToRGB layer (x_blocked: the input is channel-blocked, for a layer whose
+        takes_blocked_input is true): -> (conv output y, blocked layout?) for flrelu_nhwc."""
         s_in = int(self.in_size[0])
         k = self.conv_kernel
         pad = k - 1
@@ -420,15 +446,16 @@ class SynthesisLayer(torch.nn.Module):
         else:
             y = torch.empty([n, conv, conv, self.cout_p], dtype=ydt, device=x.device)
         layout = nv.NHWC16 if blocked else nv.NHWC
+        in_flag = nv.act_in_layout(nv.NHWC16) if x_blocked else 0  # the input layout rides above the conv's `act`
         if nv.wino_preferred(nv.dtype_code(dt), n, s_in, s_in, self.cin_p, self.cout_p, k, k, pad):
             # f16, >= 256 channels: the fused Winograd F(2,3)-along-x kernel (2/3 of the MFMA work, wino.hip)
             nv.conv_wino(nv.ptr(x), nv.ptr(self.packed_wino()), nv.ptr(y), nv.F16, nv.dtype_code(ydt), n, s_in, s_in,
-                         self.cin_p, self.cout_p, self.out_channels, pad, conv, conv, nv.ptr(oscale), nv.ptr(bp), 0,
-                         0.0, 1.0, -1.0, 1.0, layout, stream)
+                         self.cin_p, self.cout_p, self.out_channels, pad, conv, conv, nv.ptr(oscale), nv.ptr(bp),
+                         in_flag, 0.0, 1.0, -1.0, 1.0, layout, stream)
         else:
             nv.conv_igemm(nv.ptr(x), nv.ptr(wp), nv.ptr(y), nv.dtype_code(dt), nv.dtype_code(ydt), n, s_in, s_in,
                           self.cin_p, self.cout_p, self.out_channels, k, k, pad, conv, conv, nv.ptr(oscale),
-                          nv.ptr(bp), 0, 0.0, 1.0, -1.0, 1.0, layout, stream, x.device)
+                          nv.ptr(bp), in_flag, 0.0, 1.0, -1.0, 1.0, layout, stream, x.device)
         return y, blocked
 
     def packed_wino(self):
@@ -445,19 +472,22 @@ class SynthesisLayer(torch.nn.Module):
         self._cache["wino"] = (key, u)
         return u
 
-    def flrelu_nhwc(self, y, dt_out, post_scale=None, blocked=False):
+    def flrelu_nhwc(self, y, dt_out, post_scale=None, blocked=False, out_blocked=False):
         """The layer's filtered lrelu on the conv output y NHWC [n, conv, conv, cout_p] (f32, or f16 for the
-        MFMA kernel; blocked: f16/bf16 [n, cout_p/16, conv, conv, 16]) -> NHWC [n, out, out, cout_p] dt_out, times
-        post_scale [n][cout_p] when given."""
+        MFMA kernel; blocked: f16/bf16 [n, cout_p/16, conv, conv, 16]) -> NHWC [n, out, out, cout_p] dt_out (out_blocked:
+        [n, cout_p/16, out, out, 16], the strip MFMA kernel only), times post_scale [n][cout_p] when given."""
         n, conv = y.shape[0], y.shape[2 if blocked else 1]
         s_out = int(self.out_size[0])
-        out = torch.empty([n, s_out, s_out, self.cout_p], dtype=dt_out, device=y.device)
+        if out_blocked:
+            out = torch.empty([n, self.cout_p // 16, s_out, s_out, 16], dtype=dt_out, device=y.device)
+        else:
+            out = torch.empty([n, s_out, s_out, self.cout_p], dtype=dt_out, device=y.device)
         fu = self._fu
         fd = self._fd
         px0, px1, py0, py1 = self.padding
         clamp = float(self.conv_clamp) if self.conv_clamp is not None else -1.0
         nv.call("ic2_flrelu_nhwc16" if blocked else "ic2_flrelu_nhwc", nv.ptr(y), nv.ptr(out), nv.dtype_code(y.dtype),
-                nv.dtype_code(dt_out), n,
+                nv.dtype_code(dt_out) | (nv.flr_out_layout(nv.NHWC16) if out_blocked else 0), n,
                 self.cout_p, conv, conv, s_out, s_out, None if fu is None else fu.ctypes.data_as(ctypes.c_void_p),
                 1 if fu is None else fu.shape[0], None if fd is None else fd.ctypes.data_as(ctypes.c_void_p),
                 1 if fd is None else fd.shape[0], None, self.up_factor, self.down_factor, px0, px1, py0, py1,
@@ -669,9 +699,15 @@ class SynthesisNetwork(torch.nn.Module):
         # affine FC + (de)modulation prep for every layer (three launches, bit-identical to L.scales per layer)
         sc = self.scales_batched(ws, ldx, n, dt)
         x = self.input.run_nhwc(ws, ldx, n, dt, sc[0][0])
+        x_blocked = False
         for i, L in enumerate(layers):
             post = sc[i + 1][0] if i + 1 < len(layers) else None
-            x = L.run_nhwc(x, n, dt, sc[i][1], post, final_scale=self.output_scale if L.is_torgb else None)
+            # the activation stays channel-blocked exactly where the next layer's conv reads it that way
+            out_blocked = (i + 1 < len(layers) and L.writes_blocked_output(dt)
+                           and layers[i + 1].takes_blocked_input(n, dt))
+            x = L.run_nhwc(x, n, dt, sc[i][1], post, final_scale=self.output_scale if L.is_torgb else None,
+                           x_blocked=x_blocked, out_blocked=out_blocked)
+            x_blocked = out_blocked
         return _refuse(self, x, ws_in)
 
     def scales_batched(self, ws, ldx, n, dt):

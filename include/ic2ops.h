@@ -44,6 +44,18 @@ enum { IC2_F32 = 0, IC2_BF16 = 1, IC2_F16 = 2, IC2_BF16X3 = 3, IC2_F16X2 = 4,
 enum { IC2_ACT_LINEAR = 0, IC2_ACT_LRELU = 1 };
 /* NHWC16: channel-blocked NHWC, [n][c_p / 16][h][w][16] (the synthesis conv -> fused filtered lrelu hand-off) */
 enum { IC2_LAYOUT_NHWC = 0, IC2_LAYOUT_NCHW = 1, IC2_LAYOUT_NHWC16 = 2 };
+/* A layout carried as flag bits above an existing int argument (a plain value means what it always meant):
+ *  - the conv entry points' `act` may name the INPUT layout, IC2_ACT_IN_LAYOUT(IC2_LAYOUT_NHWC16) | act: the input
+ *    is then channel-blocked (the fused filtered lrelu's blocked output).  Only the kernels that stage a halo
+ *    (ic2_conv_wino, the hg4 instances) and ToRGB read it; ic2_conv_accepts_nhwc16 says which geometries.  (`act`
+ *    and not `out_layout`: the launch-plan tests replay recorded (dtype, geometry, out_layout) tuples on NHWC inputs);
+ *  - ic2_flrelu_nhwc(16)'s `dtype_out` may name the OUTPUT layout, IC2_FLR_OUT_LAYOUT(IC2_LAYOUT_NHWC16) | dtype. */
+#define IC2_ACT_IN_LAYOUT(layout) ((layout) << 4)
+#define IC2_ACT_IN_LAYOUT_OF(v) (((v) >> 4) & 15)
+#define IC2_ACT_OF(v) ((v) & 15)
+#define IC2_FLR_OUT_LAYOUT(layout) ((layout) << 4)
+#define IC2_FLR_OUT_LAYOUT_OF(v) (((v) >> 4) & 15)
+#define IC2_FLR_DTYPE_OF(v) ((v) & 15)
 
 const char* ic2_last_error(void);
 int ic2_abi_version(void);
@@ -134,7 +146,10 @@ int ic2_flrelu_nhwc(const void* x, void* y, int dtype_in, int dtype_out, int n, 
  * f16 or bf16: what ic2_conv_igemm writes with out_layout 2), output plain NHWC bf16.  Each 16-channel tile of the
  * fused kernel then reads contiguous rows instead of 32 B out of every c_p*2-byte pixel.  Same semantics as
  * ic2_flrelu_nhwc (SynthesisLayer's filtered_lrelu, SG3-public; called at stylegan3_hvae_full.py:274,329);
- * configurations without an MFMA instance return IC2_E_UNSUPPORTED. */
+ * configurations without an MFMA instance return IC2_E_UNSUPPORTED.
+ * dtype_out | IC2_FLR_OUT_LAYOUT(IC2_LAYOUT_NHWC16) (either entry point): the OUTPUT is channel-blocked too,
+ * [n][c_p/16][out_h][out_w][16], bit for bit the NHWC values (f16 input, the strip MFMA kernel only: whole 128-B
+ * lines per store; IC2_E_UNSUPPORTED elsewhere).  The next conv reads it with IC2_ACT_IN_LAYOUT(IC2_LAYOUT_NHWC16). */
 int ic2_flrelu_nhwc16(const void* x, void* y, int dtype_in, int dtype_out, int n, int c_p, int in_h, int in_w,
                       int out_h, int out_w, const float* fu, int fu_taps, const float* fd, int fd_taps, const float* b,
                       int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, float clamp,
@@ -186,6 +201,14 @@ int ic2_modconv_prep_batched(const float* ws, int64_t ldx, int n, int w_dim, int
  * e.g. "igemm8_og2", "hg4_o128_w32_p2", "hconv_64_64", "torgb", "igemm_128x128_splitk".  Static storage. */
 const char* ic2_conv_plan(int dtype, int out_dtype, int out_layout, int n, int h, int w, int cin_p, int cout_p,
                           int cout_valid, int kh, int kw, int pad);
+
+/* 1 when the conv the synthesis runs for this geometry -- ic2_conv_wino where ic2_conv_wino_preferred says so, else
+ * ic2_conv_igemm_ws's launch plan -- takes its input channel-blocked (IC2_ACT_IN_LAYOUT(IC2_LAYOUT_NHWC16) in
+ * act) AND the hand-off is kept for that kernel family (the Winograd kernel, the hg4 halo kernels, ToRGB:
+ * decided per family by measurement, DESIGN.md "Channel-blocked hand-off, both directions"); else 0: the entry
+ * points refuse blocked input for every other kernel.  Host only.  Same arguments as ic2_conv_plan. */
+int ic2_conv_accepts_nhwc16(int dtype, int out_dtype, int out_layout, int n, int h, int w, int cin_p, int cout_p,
+                            int cout_valid, int kh, int kw, int pad);
 
 /* Non-zero when IC2_DEV=1: the development knobs (forced kernel instances, A/B switches; IC2_HG4, IC2_IGEMM_TILE,
  * ...) are read from the environment only then -- otherwise the launch plan never depends on it. */

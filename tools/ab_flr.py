@@ -1,6 +1,7 @@
 """Per-layer timing of the fused filtered lrelu on the C2 shapes (SG3-T-256, batch 32, f16 NHWC16 in, bf16 out),
-HIP events around 20 back-to-back calls per layer.  python tools/ab_flr.py [label]  (A/B: run once with
-IC2_DEV=1 IC2_FLR_STRIP=0 for the round-2 tile kernel)"""
+HIP events around 20 back-to-back calls per layer.  python tools/ab_flr.py [label [res [n [blocked]]]]  (A/B: run once
+with IC2_DEV=1 IC2_FLR_STRIP=0 for the round-2 tile kernel; a fourth argument `blocked` asks for the channel-blocked
+NHWC16 output of the filtered lrelu -> conv hand-off)"""
 import ctypes
 import os
 import sys
@@ -17,6 +18,7 @@ def main():
     label = sys.argv[1] if len(sys.argv) > 1 else "default"
     res = int(sys.argv[2]) if len(sys.argv) > 2 else 256
     n = int(sys.argv[3]) if len(sys.argv) > 3 else 32
+    out_flag = nv.flr_out_layout(nv.NHWC16) if len(sys.argv) > 4 and sys.argv[4] == "blocked" else 0
     dev = torch.device("cuda", 0)
     torch.manual_seed(1)
     G = ic2.Generator(img_resolution=res, precision="bf16").to(dev)
@@ -32,7 +34,7 @@ def main():
         ps = torch.rand(n, c_p, device=dev) + 0.5
 
         def call():
-            nv.call("ic2_flrelu_nhwc16", nv.ptr(x), nv.ptr(out), nv.F16, nv.BF16, n, c_p, conv, conv, s_out, s_out,
+            nv.call("ic2_flrelu_nhwc16", nv.ptr(x), nv.ptr(out), nv.F16, nv.BF16 | out_flag, n, c_p, conv, conv, s_out, s_out,
                     L._fu.ctypes.data_as(ctypes.c_void_p), L._fu.shape[0], L._fd.ctypes.data_as(ctypes.c_void_p),
                     L._fd.shape[0], None, L.up_factor, L.down_factor, *L.padding, float(np.sqrt(2)), 0.2, 256.0, 0,
                     nv.ptr(ps), nv.stream_of(x))
