@@ -1,5 +1,6 @@
-// Conv helpers shared by the implicit-GEMM (igemm.hip) and Winograd (wino.hip) kernels: MFMA operand types, the
-// launch argument record, the fused epilogue store and the XCD-aware block remap.
+// Device-side conv helpers shared by the implicit-GEMM (igemm.hip, igemm8.hip), halo (hg4.hip, hconv.hip) and Winograd
+// (wino.hip) kernels: MFMA operand types, the launch argument record, the fused epilogue store, the implicit GEMMs'
+// epilogue and tile order, and the XCD-aware block remap.  The host side (launch plan, launchers) is conv_plan.h.
 #pragma once
 #include "common.h"
 
@@ -159,7 +160,66 @@ __device__ __forceinline__ int xcd_remap(int b, int nblocks) {
   return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
 }
 
-constexpr uint32_t kOob = 0x7ffffff0u;            // num_records of a live descriptor = the zero-answer offset
+// Epilogue shared by the implicit-GEMM kernels (igemm.hip, igemm8.hip): lane holds
+// C[o = obase + 16i + 4*fh + r][p = pbase + 16j + fr].  A split-K slice (gridDim.y > 1) stores its raw partial sums
+// instead.
+template <int I, int J>
+__device__ __forceinline__ void ig_epilogue(const IgemmArgs& a, const f32x4 (&acc)[I][J], int obase, int pbase, int fr,
+                                            int fh) {
+  const int hw = a.ho * a.wo;
+  if (gridDim.y > 1) {  // split-K slice: raw partial sums
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const int p = pbase + j * 16 + fr;
+      if (p >= a.M) continue;
+#pragma unroll
+      for (int i = 0; i < I; ++i) {
+        const int ob = obase + i * 16 + 4 * fh;
+        if (ob < a.cout_p) *reinterpret_cast<f32x4*>(a.ws + ((int64_t)blockIdx.y * a.M + p) * a.cout_p + ob) = acc[i][j];
+      }
+    }
+    return;
+  }
+  // bias for every channel block, then per 16-pixel column the oscale rows of its samples (a wave's pixels may
+  // span two samples), loaded before that column's stores
+  float4 bi[I];
+#pragma unroll
+  for (int i = 0; i < I; ++i) bi[i] = ig_load_bias(a, obase + i * 16 + 4 * fh);
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int p = pbase + j * 16 + fr;
+    const int pc = p < a.M ? p : a.M - 1;
+    const int nn = pc / hw;
+    const int pix = pc - nn * hw;
+    float4 sc[I];
+#pragma unroll
+    for (int i = 0; i < I; ++i) sc[i] = ig_load_oscale(a, nn, obase + i * 16 + 4 * fh);
+    ig_preloads_done();
+    if (p >= a.M) continue;
+#pragma unroll
+    for (int i = 0; i < I; ++i) {
+      const int ob = obase + i * 16 + 4 * fh;
+      if (ob >= a.cout_p) continue;
+      const float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+      ig_store4v(a, p, nn, pix, ob, v, sc[i], bi[i]);
+    }
+  }
+}
+
+// logical tile -> (o_tile, p_tile), bijective: runs of `group` consecutive p-tiles sweep one o-tile at a
+// time, so the blocks resident on one XCD at once share a single weight panel in its L2 (all o-tiles of
+// a p-tile side by side would keep tiles_o panels live).  The last run may be shorter.
+__device__ __forceinline__ void tile_coords(int logical, int tiles_o, int tiles_p, int group, int& o_tile,
+                                            int& p_tile) {
+  const int per = group * tiles_o;
+  const int gi = logical / per;
+  const int rem = logical - gi * per;
+  const int gsz = min(group, tiles_p - gi * group);
+  o_tile = rem / gsz;
+  p_tile = gi * group + (rem - o_tile * gsz);
+}
+
+constexpr uint32_t kOob = 0x7ffffff0u;           // num_records of a live descriptor = the zero-answer offset
 constexpr int kRsrcWord3 = 0x00020000;            // raw buffer descriptor word 3 (gfx9 family)
 
 }  // namespace ic2

@@ -1,6 +1,6 @@
 // HVAE_VGG_Encoder support kernels (/root/reference/stylegan3_hvae_full.py:105-247) and the metric /
 // resize helpers of the compressor API.  All HBM-bound; NHWC with padded channel stride c_p.
-#include "common.h"
+#include "conv_plan.h"  // conv_gn_*: the conv with the GroupNorm partial sums fused into the halo kernels' epilogue
 
 #include <algorithm>
 #include <type_traits>
@@ -16,7 +16,7 @@ static int grid_1d(int64_t total, int per = 1) {
 
 // Split-bf16 activations (ic2ops.h IC2_BF16X3): logical channel stride c_p stored as 2 * c_p bf16 channels
 // [hi | lo] per pixel, hi = bf16(v), lo = bf16(v - hi) (v - hi is exact in f32).  (Round 3 stored [hi | hi | lo];
-// the convs now read the hi block twice through their K mapping, igemm.hip ig_xb32.)
+// the convs now read the hi block twice through their K mapping, conv_common.h ig_xb32.)
 struct bf16x3_t {
   bf16_t v;
 };
@@ -351,7 +351,7 @@ __global__ void __launch_bounds__(256) gn_apply_oct_kernel(const TI* __restrict_
       ld8(yb + (int64_t)idx * c_p, v);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        float t = __builtin_fmaf(v[k] - mu[k], sc[k], sh[k]);  // as gn_lrelu_bf16x8 (igemm.hip), bit for bit
+        float t = __builtin_fmaf(v[k] - mu[k], sc[k], sh[k]);  // as gn_lrelu_bf16x8 (hconv.hip), bit for bit
         t = t < 0.f ? t * slope : t;
         res[k] = accum ? res[k] + t : t;
       }
@@ -514,17 +514,6 @@ __global__ void __launch_bounds__(256) resize_bilinear_kernel(const float* __res
     y[e] = v;
   }
 }
-
-// igemm.hip: the conv with the GroupNorm partial sums fused into the halo conv's epilogue
-int conv_gn_fused(const void* x, const void* w, void* y, int dtype, int n, int h, int w_, int cin_p, int cout_p,
-                  int cout_valid, int kh, int kw, int pad, const float* bias, int groups, double* part,
-                  int64_t part_doubles, void* workspace, int64_t ws_bytes, int fuse_mode, hipStream_t s,
-                  const float* in_gn, float in_slope, float out_mul = 1.f);
-bool conv_gn_in_supported(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw, int pad);
-bool conv_gn_fuses(int dtype, int n, int h, int w_, int cin_p, int cout_p, int cout_valid, int kh, int kw, int pad,
-                   int groups, int fuse_mode);
-int64_t conv_gn_fused_part_doubles(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw, int pad,
-                                   int groups);
 
 }  // namespace ic2
 

@@ -214,7 +214,7 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
     }
   };
 
-  // Schedule (the 8-phase kernel's ping-pong, igemm.hip): every K-step (cb, ky) is two R/M section pairs, one per
+  // Schedule (the 8-phase kernel's ping-pong, igemm8.hip): every K-step (cb, ky) is two R/M section pairs, one per
   // 64-channel half of the U slab; R = that half-slab's 8 A fragments, V / input work, this wave's DMAs, counted
   // vmcnt, barrier; M = 16 MFMAs, barrier.  Waves 4-7 run one barrier behind, so on every SIMD one wave's MFMAs
   // overlap the other's R.   R_0(s): V_s from d(s), A(o 0..63);  R_1(s): A(o 64..127), d(s+1) read.

@@ -19,8 +19,8 @@ elif [ $kind = wino ]; then src=wino.hip; def=IC2_WX_ABL; tag=wxabl;
 elif [ $kind = winostamp ]; then src=wino.hip; def=IC2_WX_STAMP; tag=wxstamp;
 elif [ $kind = winosched ]; then src=wino.hip; def=IC2_WX_SCHED; tag=wxsched;
 elif [ $kind = winoprio ]; then src=wino.hip; def=IC2_WX_PRIO; tag=wxprio;
-elif [ $kind = hg4pair ]; then src=igemm.hip; def=IC2_HG4_PAIR; tag=hg4pair;
-else src=igemm.hip; def=IC2_HG4_ABL; tag=hg4abl; fi
+elif [ $kind = hg4pair ]; then src=hg4.hip; def=IC2_HG4_PAIR; tag=hg4pair;
+else src=hg4.hip; def=IC2_HG4_ABL; tag=hg4abl; fi
 for abl in "$@"; do
   d=image_compression_2_amd/_build_$tag$abl; mkdir -p $d
   objs=""
