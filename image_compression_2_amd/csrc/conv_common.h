@@ -67,6 +67,9 @@ struct IgemmArgs {
   // f16 output converted IEEE (out_dtype IC2_F16_IEEE at the entry point: the training path's gradient convs) instead
   // of saturated to the f16 range (activations)
   int out_ieee;
+  // Winograd kernel: 0 = a 16-lane pair block is 16 pairs of one tile row (wx_ns blocks per row); 1 = the tile's
+  // wx_th * wx_twp <= 128 pair slots are numbered row-major and cut into blocks of 16 (wx_ns unused)
+  int wx_flat;
 };
 __device__ __forceinline__ int ig_xb32(const IgemmArgs& a, int b) { return b >= a.x_hb32 ? b - a.x_hb32 : b; }
 // Byte offset, from the first K block of sample 0, of 16-B chunk `chunk` (0..3: 8 channels each) of the 32-channel K

@@ -23,12 +23,17 @@
 //   U slab of a step: rows (nu, o) x 32 channels = 32 KiB, a 3-slab ring (slab s+2 issued at step s).
 //   Halo of a block: the (wx_th + 2) input rows x (2 wx_twp + 2) pixels x 32 channels, stored de-interleaved
 //   ([row][x parity][x / 2], wx_hp = wx_twp + 1 64-B LDS rows per line), double-buffered, issued as one burst at the
-//   block's first kernel row.  A 16-lane pair block is 16 consecutive pairs of ONE output row (a tile row is served
-//   by wx_ns blocks), so a fragment read covers 16 consecutive LDS rows of one line.
+//   block's first kernel row.  Row-blocked tiles: a 16-lane pair block is 16 consecutive pairs of ONE output row (a
+//   tile row is served by wx_ns blocks), so a fragment read covers 16 consecutive LDS rows of one line.  Flat tiles
+//   (wx_flat): the wx_th * wx_twp <= 128 pair slots are numbered row-major and cut into blocks of 16, so a block may
+//   wrap from one tile row into the next (no whole blocks of padding per row); only the slot -> (row, pair) mapping
+//   of the fragment offsets and of the epilogue differs (wx_slot), the K loop and the DMA plan are the same.
 //   LDS rows of 64 B.  U slab: 16-B chunk c stored at c ^ (((row >> 2) & 1) << 1) (hg4's conflict-free swizzle for 16
 //   consecutive rows).  Halo: the same swizzle on the index WITHIN the line, so any line pitch and any kernel-row
 //   shift keeps a read conflict-free (brute-forced over the ds_read_b128 lane groups; the round-5 first version,
 //   swizzled on the absolute row with lanes wrapping across output rows, spent 25 % of its LDS cycles on conflicts).
+//   A flat tile's wrapped blocks are not 16 consecutive rows: part of their reads are 2-way conflicted, counted on
+//   the host by wx_flat_conflicts and weighed by the planner (wx_tile).
 // V is formed in f16 (packed adds, one rounding per add; the CPU emulation tools/wino_emu.py prices the rounding).
 #include "conv_common.h"
 
@@ -63,6 +68,19 @@ __device__ __forceinline__ f16x8 wx_add(f16x8 a, f16x8 b) {
 __device__ __forceinline__ int wx_off(int row, int chunk) { return row * 64 + ((chunk ^ (((row >> 2) & 1) << 1)) << 4); }
 __device__ __forceinline__ int wx_hoff(int line, int hp, int idx, int chunk) {
   return (line * hp + idx) * 64 + ((chunk ^ (((idx >> 2) & 1) << 1)) << 4);
+}
+// Lane fr of pair block b -> (tile row r, pair t); false for a slot that stores nothing.  Row-blocked: block b is the
+// 16 pairs (b % ns) * 16 .. of tile row b / ns.  Flat: slot 16 b + fr of the th x twp slots numbered row-major.
+__device__ __forceinline__ bool wx_slot(const IgemmArgs& a, int b, int fr, int& r, int& t) {
+  if (a.wx_flat) {
+    const int s = 16 * b + fr;
+    r = s / a.wx_twp;
+    t = s - r * a.wx_twp;
+    return s < a.wx_th * a.wx_twp;
+  }
+  r = b / a.wx_ns;
+  t = (b % a.wx_ns) * 16 + fr;
+  return r < a.wx_th && t < a.wx_twp;
 }
 
 // diagnostic builds only (wrong results; tools/build_abl.sh wino): IC2_WX_ABL bit 0 skips the U DMAs after the first
@@ -142,15 +160,17 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
     const bool ok = l < a.wx_nh && (unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w_;
     h_off[k] = ok ? ig_halo_off(a, nn, iy, ix, pch ^ (((idx >> 2) & 1) << 1)) : kOob;
   }
-  // input-fragment offsets at ky = 0: pair block b = 2 pg + jb is 16 pairs of tile row b / ns; this half's 3 of the
-  // pair's 4 pixels (half + m, m < 3: positions 0, 1 use pixels 0..2, positions 2, 3 pixels 1..3).  Lanes past the
-  // tile's pairs read past their line (conflict-free, unused); blocks past the tile's rows repeat its last row.
+  // input-fragment offsets at ky = 0 of the pair slots (wx_slot) of pair blocks b = 2 pg + jb; this half's 3 of the
+  // pair's 4 pixels (half + m, m < 3: positions 0, 1 use pixels 0..2, positions 2, 3 pixels 1..3).  Row-blocked:
+  // lanes past the tile's pairs read past their line (conflict-free, unused); blocks past the tile's rows repeat its
+  // last row.  Flat: slots past the tile all read the tile's last slot (one address: a broadcast).
   int boff[2][3];
-  const int ns = a.wx_ns;
 #pragma unroll
   for (int jb = 0; jb < 2; ++jb) {
-    const int b = pg * 2 + jb;
-    const int rr = min(b / ns, a.wx_th - 1), t = (b % ns) * 16 + fr;
+    int rr, t;
+    const bool live = wx_slot(a, pg * 2 + jb, fr, rr, t);
+    if (a.wx_flat && !live) t = twp - 1;
+    rr = min(rr, a.wx_th - 1);
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
       const int j = half + m;
@@ -391,9 +411,8 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
   ig_preloads_done();
 #pragma unroll
   for (int jb = 0; jb < 2; ++jb) {
-    const int b = pg * 2 + jb;
-    const int r = b / ns, t = (b % ns) * 16 + fr;
-    if (r >= a.wx_th || t >= twp) continue;
+    int r, t;
+    if (!wx_slot(a, pg * 2 + jb, fr, r, t)) continue;
     const int oy = oy0 + r, ox = 2 * (px0 + t);
     if (oy >= a.ho || ox >= a.wo) continue;
     const int pix = oy * a.wo + ox;
@@ -466,13 +485,69 @@ __global__ void __launch_bounds__(256) pack_wino_kernel(const float* __restrict_
 // The tile of one launch: th rows x twp pairs, each row served by ns 16-lane pair blocks (th * ns <= 8 blocks,
 // twp <= 16 ns), halo (th + 2) * 2 * (twp + 1) <= WX_HROWS rows; fewest rounds of one workgroup per CU over the chip's
 // 256 CUs, then fewest workgroups, then full pair blocks.
+//
+// Flat tiles: th rows x twp pairs whose th * twp <= 128 slots are numbered row-major and cut into the 8 blocks of 16, so
+// a block may start in one row and end in the next and a row of 27, 43 or 75 pairs (the pad-2 synthesis convs) no
+// longer costs ceil(pairs / 16) whole blocks.  A wrapped block's input-fragment read is no longer 16 consecutive LDS
+// rows of one line, so some of the 96 (block, pixel, kernel row) reads of a K-block are 2-way bank-conflicted
+// (wx_flat_conflicts; the A-fragment reads are not affected).
 struct WxTile {
-  int twp, th, ns, hp, nh, tx, ty, to;
+  int twp, th, ns, hp, nh, tx, ty, to, flat;
   int64_t blocks;
+  int64_t rounds() const { return ceil_div(blocks, 256); }
 };
-static WxTile wx_tile(int n, int ho, int wo, int cout_p) {
-  static const int force_twp = knob("IC2_WINO_TWP", 0), force_th = knob("IC2_WINO_TH", 0);
-  const int pairs = (wo + 1) / 2;
+static WxTile wx_make_tile(int twp, int th, int ns, int flat, int n, int ho, int wo, int cout_p) {
+  WxTile t;
+  t.twp = twp; t.th = th; t.ns = ns; t.flat = flat; t.hp = twp + 1; t.nh = (th + 2) * 2 * t.hp;
+  t.tx = (int)ceil_div((wo + 1) / 2, twp);
+  t.ty = (int)ceil_div(ho, th);
+  t.to = (int)ceil_div(cout_p, WX_BO);
+  t.blocks = (int64_t)n * t.tx * t.ty * t.to;
+  return t;
+}
+
+// Input-fragment reads of a flat tile, out of the 96 (pair block, pixel of the pair's 4, kernel row) per K-block, in
+// which two lanes of one ds_read_b128 lane group hit the same 16-B residue of the 256-B bank row at different
+// addresses (2-way conflict: one more LDS cycle for that group).  Lane groups of 16 within a half wave: lanes
+// {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} (lane = 16 fh + fr; the upper half wave is the same picture with its
+// chunks XORed by 2).  Addresses as the kernel forms them: wx_slot's flat mapping, idle slots on the last live slot,
+// line pitch `pitch`, wx_hoff's swizzle on the index within the line.
+static int wx_flat_conflicts(int twp, int th, int pitch) {
+  const int live = th * twp;
+  int bad = 0;
+  for (int b = 0; b < 8; ++b)
+    for (int j = 0; j < 4; ++j)
+      for (int ky = 0; ky < 3; ++ky) {
+        bool conflict = false;
+        for (int g = 0; g < 2; ++g) {
+          int seen[16];
+          for (int i = 0; i < 16; ++i) seen[i] = -1;
+          for (int fh = 0; fh < 2; ++fh)
+            for (int fr = 0; fr < 16; ++fr) {
+              const bool outer = fr < 4 || fr >= 12;
+              if ((fh == g) != outer) continue;
+              const int s = 16 * b + fr < live ? 16 * b + fr : live - 1;
+              const int r = s / twp, t = s - r * twp;
+              const int idx = t + (j >> 1), row = ((r + ky) * 2 + (j & 1)) * pitch + idx;
+              const int res = (row & 3) * 4 + (fh ^ (((idx >> 2) & 1) << 1));
+              if (seen[res] >= 0 && seen[res] != row) conflict = true;
+              seen[res] = row;
+            }
+        }
+        bad += conflict;
+      }
+  return bad;
+}
+
+// WX_FLAT_MARGIN_PCT: a flat tile is planned only where it saves at least this share of the best row-blocked tile's
+// rounds (the 2-way conflicts of its wrapped reads cost part of what the saved rounds gain).  From the forced-tile
+// sweep of profiles/r9_wino_flat_ab.txt (SG3-T-256 at batch 32, SG3-T-1024 at batch 8): every flat tile that saved
+// rounds won outside the spread of repeated runs, the smallest saving measured being 23 of 24 rounds (4.2 %: -2.1 %
+// in time on the 150 x 150 x 256 conv); every flat tile at equal rounds measured level or slower (+0.4 .. +2 %).
+// IC2_WINO_FLAT (dev knob): 0 = row-blocked tiles only, 1 = the rule above, 2 = flat tiles only.
+constexpr int WX_FLAT_MARGIN_PCT = 4;
+
+static WxTile wx_tile_rows(int n, int ho, int wo, int cout_p, int force_twp, int force_th) {
   WxTile best{};
   int64_t best_rounds = -1;
   for (int ns = 1; ns <= 8; ns *= 2)
@@ -480,15 +555,9 @@ static WxTile wx_tile(int n, int ho, int wo, int cout_p) {
       if (force_th && th != force_th) continue;
       for (int twp = 1; twp <= 16 * ns; ++twp) {
         if (force_twp && twp != force_twp) continue;
-        const int hp = twp + 1, nh = (th + 2) * 2 * hp;
-        if (nh > WX_HROWS) break;
-        WxTile t;
-        t.twp = twp; t.th = th; t.ns = ns; t.hp = hp; t.nh = nh;
-        t.tx = (int)ceil_div(pairs, twp);
-        t.ty = (int)ceil_div(ho, th);
-        t.to = (int)ceil_div(cout_p, WX_BO);
-        t.blocks = (int64_t)n * t.tx * t.ty * t.to;
-        const int64_t rounds = ceil_div(t.blocks, 256);
+        if ((th + 2) * 2 * (twp + 1) > WX_HROWS) break;
+        const WxTile t = wx_make_tile(twp, th, ns, 0, n, ho, wo, cout_p);
+        const int64_t rounds = t.rounds();
         // ties: the fewest workgroups, then full 16-pair blocks (16 x 8 beat 15 x 8 at equal counts by 0.4-1.3 % on
         // the SG3-T-256 148-px layers, profiles/r5_wino_tile_sweep.txt)
         const bool full = twp % 16 == 0, best_full = best.twp % 16 == 0;
@@ -500,6 +569,49 @@ static WxTile wx_tile(int n, int ho, int wo, int cout_p) {
       }
     }
   return best;
+}
+// the best flat tile: fewest rounds, fewest workgroups, fewest conflicted fragment reads, smallest halo
+static WxTile wx_tile_flat(int n, int ho, int wo, int cout_p, int force_twp, int force_th) {
+  WxTile best{};
+  int best_conf = 0;
+  for (int th = 1; th <= 128; ++th) {
+    if (force_th && th != force_th) continue;
+    for (int twp = 1; th * twp <= 128; ++twp) {
+      if (force_twp && twp != force_twp) continue;
+      if ((th + 2) * 2 * (twp + 1) > WX_HROWS) break;
+      const WxTile t = wx_make_tile(twp, th, 0, 1, n, ho, wo, cout_p);
+      if (best.blocks > 0 && (t.rounds() > best.rounds() || (t.rounds() == best.rounds() && t.blocks > best.blocks)))
+        continue;
+      const int conf = wx_flat_conflicts(twp, th, t.hp);
+      if (best.blocks > 0 && t.rounds() == best.rounds() && t.blocks == best.blocks &&
+          (conf > best_conf || (conf == best_conf && t.nh >= best.nh)))
+        continue;
+      best = t;
+      best_conf = conf;
+    }
+  }
+  return best;
+}
+static WxTile wx_tile_search(int n, int ho, int wo, int cout_p, int mode, int force_twp, int force_th) {
+  const WxTile rows = wx_tile_rows(n, ho, wo, cout_p, force_twp, force_th);
+  if (mode == 0) return rows;
+  const WxTile flat = wx_tile_flat(n, ho, wo, cout_p, force_twp, force_th);
+  if (mode == 2 || rows.blocks == 0) return flat;
+  if (flat.blocks == 0) return rows;
+  return flat.rounds() * 100 <= rows.rounds() * (100 - WX_FLAT_MARGIN_PCT) ? flat : rows;
+}
+static WxTile wx_tile(int n, int ho, int wo, int cout_p) {
+  static const int force_twp = knob("IC2_WINO_TWP", 0), force_th = knob("IC2_WINO_TH", 0);
+  static const int mode = knob("IC2_WINO_FLAT", 1);
+  // the search runs once per geometry and thread (a model has a handful): the last 16 plans are kept
+  struct Memo { int n, ho, wo, cout_p; WxTile t; };
+  static thread_local Memo memo[16];
+  static thread_local int memo_n = 0;
+  for (int i = 0; i < (memo_n < 16 ? memo_n : 16); ++i)
+    if (memo[i].n == n && memo[i].ho == ho && memo[i].wo == wo && memo[i].cout_p == cout_p) return memo[i].t;
+  const WxTile t = wx_tile_search(n, ho, wo, cout_p, mode, force_twp, force_th);
+  memo[memo_n++ % 16] = Memo{n, ho, wo, cout_p, t};
+  return t;
 }
 
 static int wx_chunk_n(int n, int h, int w_, int cin_p) {
@@ -552,7 +664,7 @@ extern "C" const char* ic2_conv_wino_plan(int n, int h, int w_, int cin_p, int c
   if (n <= 0 || ho <= 0 || wo <= 0 || cin_p <= 0 || cin_p % 32 || cout_p <= 0 || cout_p % 32) return "invalid";
   const WxTile t = wx_tile(wx_chunk_n(n, h, w_, cin_p), ho, wo, cout_p);
   static thread_local char buf[64];
-  snprintf(buf, sizeof(buf), "wino_fx_o128_p%dx%d_f16", t.twp, t.th);
+  snprintf(buf, sizeof(buf), "wino_fx_o128_p%dx%d%s_f16", t.twp, t.th, t.flat ? "w" : "");  // w: a flat (wrapping) tile
   return buf;
 }
 
@@ -620,6 +732,7 @@ extern "C" int ic2_conv_wino(const void* x, const void* u, void* y, int dtype, i
   a.x_pix = cin_p; a.x_hb32 = 0;
   ig_set_input_layout(a, in_blocked);
   a.wx_twp = t.twp; a.wx_th = t.th; a.wx_ns = t.ns; a.wx_hp = t.hp; a.wx_nh = t.nh; a.wx_tx = t.tx; a.wx_ty = t.ty;
+  a.wx_flat = t.flat;
   hipLaunchKernelGGL(wino_fx_f16_kernel, dim3((unsigned)t.blocks), dim3(64 * WX_NW), 0, as_stream(stream), a);
   IC2_CHECK_LAUNCH("conv_wino");
   return IC2_OK;

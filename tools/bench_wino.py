@@ -2,7 +2,11 @@
 SG3-T-256 synthesis conv shapes at batch 32, f16 operands, NHWC16 f16 output (what the synthesis path runs):
 time, algorithmic TF/s and the error of each against an fp32 torch conv of the same f16 operands.
 
-    python tools/bench_wino.py [shape ...]     (IC2_DEV=1 knobs IC2_WINO_TWP / IC2_WINO_TH force a tile)
+    python tools/bench_wino.py [shape ...]     (IC2_DEV=1 knobs IC2_WINO_TWP / IC2_WINO_TH force a tile,
+                                                IC2_WINO_FLAT=0 / 2 the row-blocked / the flat slot mapping)
+
+BW_N sets the batch, BW_WINO_ONLY=1 skips the direct kernel and the reference (tile sweeps), BW_REPEATS=k times the
+Winograd kernel k times over and reports every figure (the spread of repeated runs).
 """
 import json
 import os
@@ -17,7 +21,9 @@ sys.path.insert(0, ROOT)
 # (name, cin, cout, size_in): SG3-T-256 modulated convs (pad 2) and the hg4 layers
 SHAPES = [("s36", 512, 512, 36), ("s52", 512, 512, 52), ("s84", 512, 512, 84), ("s148", 512, 512, 148),
           ("s148b", 512, 362, 148), ("s148c", 362, 256, 148), ("s276a", 256, 181, 276), ("s276b", 181, 128, 276),
-          ("s276c", 128, 128, 276)]
+          ("s276c", 128, 128, 276),
+          # SG3-T-1024 L7 / L8 (batch 8)
+          ("s148d", 512, 323, 148), ("s276d", 323, 203, 276)]
 
 
 def main():
@@ -25,6 +31,7 @@ def main():
     dev = torch.device("cuda", 0)
     only = set(sys.argv[1:])
     n, pad = int(os.environ.get("BW_N", 32)), 2
+    wino_only, repeats = os.environ.get("BW_WINO_ONLY") == "1", int(os.environ.get("BW_REPEATS", 1))
     res = {}
     for name, ci, co, s in SHAPES:
         if only and name not in only:
@@ -56,7 +63,7 @@ def main():
         row = {"plan_direct": nv.conv_plan(nv.F16, nv.F16, nv.NHWC16, n, s, s, cip, cop, co, 3, 3, pad),
                "plan_wino": nv.wino_plan(n, s, s, cip, cop, pad)}
         flops = 2.0 * n * ho * ho * co * ci * 9
-        for tag, fn in (("direct", direct), ("wino", wino)):
+        def time_us(fn):
             for _ in range(3):
                 fn()
             torch.cuda.synchronize()
@@ -67,8 +74,17 @@ def main():
                 fn()
             e1.record()
             torch.cuda.synchronize()
-            us = e0.elapsed_time(e1) / reps * 1e3
+            return e0.elapsed_time(e1) / reps * 1e3
+        for tag, fn in (("wino", wino),) if wino_only else (("direct", direct), ("wino", wino)):
+            us = time_us(fn)
             row[tag] = [round(us, 1), round(flops / us / 1e6, 1)]
+        if repeats > 1:
+            row["wino_us_repeats"] = [row["wino"][0]] + [round(time_us(wino), 1) for _ in range(repeats - 1)]
+        if wino_only:
+            res[name] = row
+            print(name, json.dumps(row), flush=True)
+            del x, w, wp, u, yd, yw
+            continue
         # fp32 reference on the same f16 operands (first 2 images)
         wn = w * w.square().mean([1, 2, 3], keepdim=True).rsqrt()
         xr = x[:2, :, :, :ci].float().permute(0, 3, 1, 2)
