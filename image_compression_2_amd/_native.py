@@ -52,6 +52,10 @@ _SIGS = {
     "ic2_gumbel_softmax_quantize": [_P, _I64, _P, _I, _P, _F, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P,
                                     _P],
     "ic2_gumbel_softmax_quantize_dseed": [_P, _I64, _P, _I, _P, _F, _I, _P, ctypes.c_uint64, _P, _P, _P, _P, _P],
+    "ic2_gumbel_softmax_bwd_ws_bytes": [_I64],
+    "ic2_gumbel_softmax_quantize_bwd": [_P, _I64, _P, _I, _P, _F, _P, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _I64,
+                                        _P],
+    "ic2_gumbel_noise": [_P, ctypes.c_uint64, ctypes.c_uint64, _I64, _I, _P, _P],
     "ic2_bias_act": [_P, _P, _P, _I, _I64, _I64, _I64, _I, _F, _F, _F, _P],
     "ic2_upfirdn2d": [_P, _P, _I, _I64, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "ic2_filtered_lrelu": [_P, _P, _I, _I64, _I64, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _F,
@@ -125,7 +129,8 @@ _SIGS = {
 _RESTYPE = {"ic2_conv_plan": ctypes.c_char_p, "ic2_conv_wino_plan": ctypes.c_char_p, "ic2_conv_igemm_ws_bytes": _I64, "ic2_group_norm_stats_floats": _I64, "ic2_global_avg_pool_floats": _I64,
             "ic2_uint8_sse_scratch_doubles": _I64, "ic2_rc_bound": _I64, "ic2_conv_wgrad_ws_floats": _I64,
             "ic2_gn_lrelu_pool_bwd_floats": _I64, "ic2_conv3x3_gn_stats_floats": _I64,
-            "ic2_flrelu_bwd_ydot_floats": _I64, "ic2_scale_bwd_part_floats": _I64}
+            "ic2_flrelu_bwd_ydot_floats": _I64, "ic2_scale_bwd_part_floats": _I64,
+            "ic2_gumbel_softmax_bwd_ws_bytes": _I64}
 
 _lib = None
 _lock = threading.Lock()

@@ -266,6 +266,64 @@ class ToNHWC(torch.autograd.Function):
         return dx, None, None
 
 
+class GumbelSoftmaxQuantize(torch.autograd.Function):
+    """GumbelSoftmaxDiscretization.forward (gumbel_softmax_compression.py:93-127) under autograd: the reference's
+    ``train_gumbel_discretized_hvae`` (:527-567) backpropagates through it into the encoder's means and
+    ``log_temperature``.  Forward: the unchanged fused kernel (ic2_gumbel_softmax_quantize_dseed) and the perplexity
+    of its column sums -> (disc, perplexity, idx).  Backward: ic2_gumbel_softmax_quantize_bwd, which recomputes the
+    probabilities from the saved seed (or the explicit noise) instead of reading a stored [M, K] tensor; the
+    perplexity's gradient enters as the per-code vector q, built on the device from the saved column sums.  The
+    straight-through hard mode has the soft mode's gradient.  No host sync in either direction."""
+
+    @staticmethod
+    def forward(ctx, z, log_temperature, codebook, seed, hard, gumbel_noise):
+        zf = z.detach().to(torch.float32).contiguous()
+        nv.require_gpu(zf)
+        m, k = zf.numel(), codebook.numel()
+        disc = torch.empty(m, dtype=torch.float32, device=zf.device)
+        idx = torch.empty(m, dtype=torch.int64, device=zf.device)
+        psum = torch.zeros(k, dtype=torch.float32, device=zf.device)
+        logt = log_temperature.detach()
+        nv.call("ic2_gumbel_softmax_quantize_dseed", nv.ptr(zf), m, nv.ptr(codebook), k, nv.ptr(logt), 1.0,
+                int(bool(hard)), nv.ptr(seed), 0, nv.ptr(gumbel_noise), nv.ptr(disc), nv.ptr(idx), nv.ptr(psum),
+                nv.stream_of(zf))
+        avg_probs = psum / m
+        perplexity = torch.exp(-torch.sum(avg_probs * torch.log(avg_probs + 1e-10)))
+        ctx.save_for_backward(zf, logt, codebook, seed, psum, perplexity, gumbel_noise)
+        ctx.z_shape, ctx.z_dtype, ctx.hard = z.shape, z.dtype, bool(hard)
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        return disc.view(z.shape), perplexity, idx
+
+    @staticmethod
+    def backward(ctx, g_disc, g_perp, _g_idx):
+        zf, logt, codebook, seed, psum, perplexity, gumbel_noise = ctx.saved_tensors
+        m, k = zf.numel(), codebook.numel()
+        dev = zf.device
+        g = (torch.zeros(m, dtype=torch.float32, device=dev) if g_disc is None
+             else g_disc.to(torch.float32).contiguous().view(-1))
+        q = None
+        if g_perp is not None:
+            # d perplexity / d avg_k = perplexity * -(log(avg_k + 1e-10) + avg_k / (avg_k + 1e-10)); avg = mean over m
+            avg = psum / m
+            q = ((g_perp.to(torch.float32) * perplexity)
+                 * (-(torch.log(avg + 1e-10) + avg / (avg + 1e-10))) / m).contiguous()
+        dz = torch.empty(m, dtype=torch.float32, device=dev)
+        dlogt = ws = None
+        nbytes = 0
+        if ctx.needs_input_grad[1]:
+            nbytes = int(nv.query("ic2_gumbel_softmax_bwd_ws_bytes", m))
+            ws = torch.empty([max(nbytes, 4) // 4], dtype=torch.float32, device=dev)
+            dlogt = torch.empty(1, dtype=torch.float32, device=dev)
+        nv.call("ic2_gumbel_softmax_quantize_bwd", nv.ptr(zf), m, nv.ptr(codebook), k, nv.ptr(logt), 1.0,
+                nv.ptr(seed), 0, nv.ptr(gumbel_noise), nv.ptr(g), nv.ptr(q), nv.ptr(dz), nv.ptr(dlogt), nv.ptr(ws),
+                nbytes, nv.stream_of(zf))
+        if dlogt is not None:
+            dlogt = dlogt.view(logt.shape).to(logt.dtype)
+        dz = dz.view(ctx.z_shape).to(ctx.z_dtype) if ctx.needs_input_grad[0] else None
+        return dz, dlogt, None, None, None, None
+
+
 def _synth_layer_grads(L, dt, os_, y, dout, post=None):
     """Backward of one modulated synthesis layer from dL/d(filtered lrelu output) `dout`: the FLR adjoint stored
     times oscale (dL/dconv) with the per-tile sums for dL/doscale, then the dgrad implicit GEMM -> (dL/da, dL/doscale),

@@ -174,8 +174,88 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
 }
 
 __device__ __forceinline__ float gumbel_from_bits(uint32_t r) {
-  const float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
+  // (0, 1): the top draw r >> 8 = 2^24 - 1 rounds 16777215.5 up to 2^24, u = 1 and the noise to +inf (the row's
+  // softmax to NaN, once in 2^24 draws: about two latents per call at M * K = 2^25) -- held at the largest float
+  // below 1 instead (noise 16.64); every other draw is unchanged
+  const float u = fminf(((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
   return -logf(-logf(u));
+}
+
+// One latent's row on one wave, shared by the forward and the backward kernel (the backward recomputes the
+// probabilities instead of reading 4*n*k bytes back): lane l holds the entries kk = l + 64*j.
+//   y = (-|v - c| + g) / tau (masked entries -inf), e = exp(y - max y) (masked 0), soft = e * inv_s;
+//   imin = argmin |v - c|, iymax = argmax y (first index on ties, both).
+template <int KPL>
+struct GumbelRow {
+  float y[KPL], e[KPL];
+  float ymax, inv_s;
+  int imin, iymax;
+};
+
+template <int KPL>
+__device__ __forceinline__ void gumbel_row(float v, int64_t i, const float (&c)[KPL], int k, int lane, float inv_tau,
+                                           const float* __restrict__ noise, uint64_t offset, uint2 key,
+                                           GumbelRow<KPL>& row) {
+  float (&y)[KPL] = row.y;
+  float (&e)[KPL] = row.e;
+  float dmin = INFINITY;
+  int imin = 0x7fffffff;
+  float ymax = -INFINITY;
+  int iymax = 0x7fffffff;
+#pragma unroll
+  for (int j = 0; j < KPL; ++j) {
+    const int kk = lane + 64 * j;
+    if (kk < k) {
+      const float d = fabsf(v - c[j]);
+      if (d < dmin) {  // per-lane entries ascend in kk: strict < keeps the first
+        dmin = d;
+        imin = kk;
+      }
+      float g;
+      if (noise) {
+        g = noise[i * k + kk];
+      } else {
+        const uint64_t ctr = offset + (uint64_t)i * (uint64_t)k + (uint64_t)kk;
+        const uint4 r = philox4x32_10(make_uint4((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u), key);
+        g = gumbel_from_bits(r.x);
+      }
+      y[j] = (-d + g) * inv_tau;
+      if (y[j] > ymax) {
+        ymax = y[j];
+        iymax = kk;
+      }
+    } else {
+      y[j] = -INFINITY;
+    }
+  }
+  // wave reductions: argmin (first index on ties), max y (first index on ties)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float od = __shfl_xor(dmin, off, 64);
+    const int oi = __shfl_xor(imin, off, 64);
+    if (od < dmin || (od == dmin && oi < imin)) {
+      dmin = od;
+      imin = oi;
+    }
+    const float oy = __shfl_xor(ymax, off, 64);
+    const int oyi = __shfl_xor(iymax, off, 64);
+    if (oy > ymax || (oy == ymax && oyi < iymax)) {
+      ymax = oy;
+      iymax = oyi;
+    }
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < KPL; ++j) {
+    e[j] = (lane + 64 * j < k) ? expf(y[j] - ymax) : 0.f;
+    s += e[j];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  row.inv_s = 1.f / s;
+  row.ymax = ymax;
+  row.imin = imin;
+  row.iymax = iymax;
 }
 
 template <int KPL>
@@ -207,63 +287,11 @@ __global__ void __launch_bounds__(256) gumbel_softmax_kernel(const float* __rest
   const uint2 key = make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
   for (int64_t i = (int64_t)blockIdx.x * 4 + wv; i < n; i += nwaves) {
     const float v = z[i];
-    float y[KPL];
-    float dmin = INFINITY;
-    int imin = 0x7fffffff;
-    float ymax = -INFINITY;
-    int iymax = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-      const int kk = lane + 64 * j;
-      if (kk < k) {
-        const float d = fabsf(v - c[j]);
-        if (d < dmin) {  // per-lane entries ascend in kk: strict < keeps the first
-          dmin = d;
-          imin = kk;
-        }
-        float g;
-        if (noise) {
-          g = noise[i * k + kk];
-        } else {
-          const uint64_t ctr = offset + (uint64_t)i * (uint64_t)k + (uint64_t)kk;
-          const uint4 r = philox4x32_10(make_uint4((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u), key);
-          g = gumbel_from_bits(r.x);
-        }
-        y[j] = (-d + g) * inv_tau;
-        if (y[j] > ymax) {
-          ymax = y[j];
-          iymax = kk;
-        }
-      } else {
-        y[j] = -INFINITY;
-      }
-    }
-    // wave reductions: argmin (first index on ties), max y (first index on ties)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float od = __shfl_xor(dmin, off, 64);
-      const int oi = __shfl_xor(imin, off, 64);
-      if (od < dmin || (od == dmin && oi < imin)) {
-        dmin = od;
-        imin = oi;
-      }
-      const float oy = __shfl_xor(ymax, off, 64);
-      const int oyi = __shfl_xor(iymax, off, 64);
-      if (oy > ymax || (oy == ymax && oyi < iymax)) {
-        ymax = oy;
-        iymax = oyi;
-      }
-    }
-    float e[KPL];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-      e[j] = (lane + 64 * j < k) ? expf(y[j] - ymax) : 0.f;
-      s += e[j];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    const float inv_s = 1.f / s;
+    GumbelRow<KPL> row;
+    gumbel_row<KPL>(v, i, c, k, lane, inv_tau, noise, offset, key, row);
+    const float (&e)[KPL] = row.e;
+    const float inv_s = row.inv_s;
+    const int imin = row.imin, iymax = row.iymax;
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
@@ -337,6 +365,186 @@ extern "C" int ic2_gumbel_softmax_quantize_dseed(const float* z, int64_t n, cons
                 "gumbel_softmax_quantize_dseed: seed_dev is null");
   return gumbel_softmax_quantize(z, n, codebook, k, log_tau, tau, hard, 0, reinterpret_cast<const uint64_t*>(seed_dev),
                                  offset, gumbel_noise, disc_out, idx_out, prob_sum_out, stream);
+}
+
+// ================================================================================================
+// Gumbel-softmax quantizer backward (training through GumbelSoftmaxCompressor.forward,
+// gumbel_softmax_compression.py:172-200, in train_gumbel_discretized_hvae's step :527-567).  With a = the forward's
+// y, p = softmax(a), G = dL/d disc and q[k] = the per-code gradient of everything that depends on the column means
+// of ret (the perplexity, :126-127):
+//   r_k = G * c_k + q_k;  da_k = p_k * (r_k - sum_j p_j r_j);
+//   dz = -(1 / tau) * sum_k da_k * sign(z - c_k)   (sign(0) = 0, torch's abs backward);
+//   dlog tau = -sum_i sum_k da_ik * a_ik.
+// The hard mode's one-hot is detached (straight-through), so both modes share this gradient.  p is recomputed by
+// gumbel_row from the same noise (the explicit tensor, or the Philox stream of the forward's seed and offset) and
+// never stored.  sum_k da_k = 0, so dlog tau is accumulated as -sum da_k * (a_k - max a): the same value from terms
+// that are small wherever p is not.  Deterministic: dz[i] is one lane's store; dlog tau is one f32 partial per
+// workgroup, summed in index order in f64 by gumbel_dlogt_finish_kernel.  No atomics.
+// ================================================================================================
+namespace ic2 {
+
+template <int KPL>
+__global__ void __launch_bounds__(256) gumbel_softmax_bwd_kernel(const float* __restrict__ z, int64_t n,
+                                                                 const float* __restrict__ cb, int k,
+                                                                 const float* __restrict__ log_tau, float tau_const,
+                                                                 const uint64_t* __restrict__ seed_dev,
+                                                                 uint64_t offset, const float* __restrict__ noise,
+                                                                 const float* __restrict__ gdisc,
+                                                                 const float* __restrict__ q, float* __restrict__ dz,
+                                                                 float* __restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  const float tau = log_tau ? expf(log_tau[0]) : tau_const;
+  const float inv_tau = 1.f / tau;
+  float c[KPL], qv[KPL];
+#pragma unroll
+  for (int j = 0; j < KPL; ++j) {
+    const int kk = lane + 64 * j;
+    c[j] = kk < k ? cb[kk] : 0.f;
+    qv[j] = (q && kk < k) ? q[kk] : 0.f;
+  }
+  const uint64_t sd = seed_dev ? seed_dev[0] : 0;
+  const uint2 key = make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
+  float lt = 0.f;  // this lane's share of sum da * (a - max a)
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wv; i < n; i += nwaves) {
+    const float v = z[i];
+    const float g = gdisc[i];
+    GumbelRow<KPL> row;
+    gumbel_row<KPL>(v, i, c, k, lane, inv_tau, noise, offset, key, row);
+    float p[KPL], r[KPL];
+    float dot = 0.f;
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+      p[j] = row.e[j] * row.inv_s;
+      r[j] = g * c[j] + qv[j];
+      if (lane + 64 * j < k) dot += p[j] * r[j];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) dot += __shfl_xor(dot, off, 64);
+    float zs = 0.f;
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+      if (lane + 64 * j < k) {  // masked entries hold y = -inf: kept out of the products
+        const float da = p[j] * (r[j] - dot);
+        const float sgn = (float)((v > c[j]) - (v < c[j]));
+        zs += da * sgn;
+        lt += da * (row.y[j] - row.ymax);
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) zs += __shfl_xor(zs, off, 64);
+    if (lane == 0) dz[i] = -(zs * inv_tau);
+  }
+  if (part) {
+    __shared__ float sl[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) lt += __shfl_xor(lt, off, 64);
+    if (lane == 0) sl[wv] = lt;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = -(((sl[0] + sl[1]) + sl[2]) + sl[3]);
+  }
+}
+
+// dlogt[0] = sum of part[0 .. np) in f64: thread t adds its contiguous chunk in index order, thread 0 the 256 chunk
+// sums in index order (a fixed association: the same bits on every run).
+__global__ void __launch_bounds__(256) gumbel_dlogt_finish_kernel(const float* __restrict__ part, int np,
+                                                                  float* __restrict__ dlogt) {
+  __shared__ double sh[256];
+  const int per = (np + 255) / 256;
+  const int lo = threadIdx.x * per;
+  const int hi = lo + per < np ? lo + per : np;
+  double a = 0.0;
+  for (int i = lo; i < hi; ++i) a += (double)part[i];
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < 256; ++i) t += sh[i];
+    dlogt[0] = (float)t;
+  }
+}
+
+// The [n][k] noise the fused kernels draw for (seed, offset): element (i, kk) from counter offset + i*k + kk.
+__global__ void __launch_bounds__(256) gumbel_noise_kernel(uint64_t seed, const uint64_t* __restrict__ seed_dev,
+                                                           uint64_t offset, int64_t total, float* __restrict__ out) {
+  const uint64_t sd = seed_dev ? seed_dev[0] : seed;
+  const uint2 key = make_uint2((uint32_t)sd, (uint32_t)(sd >> 32));
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += stride) {
+    const uint64_t ctr = offset + (uint64_t)t;
+    const uint4 r = philox4x32_10(make_uint4((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u), key);
+    out[t] = gumbel_from_bits(r.x);
+  }
+}
+
+static int64_t gumbel_grid(int64_t n) {
+  int64_t g = ceil_div(n, 4);
+  return g > 4096 ? 4096 : (g < 1 ? 1 : g);
+}
+
+}  // namespace ic2
+
+extern "C" int64_t ic2_gumbel_softmax_bwd_ws_bytes(int64_t n) {
+  return n <= 0 ? 0 : ic2::gumbel_grid(n) * (int64_t)sizeof(float);
+}
+
+extern "C" int ic2_gumbel_softmax_quantize_bwd(const float* z, int64_t n, const float* codebook, int k,
+                                               const float* log_tau, float tau, const int64_t* seed_dev,
+                                               uint64_t offset, const float* gumbel_noise, const float* grad_disc,
+                                               const float* q, float* dz_out, float* dlogt_out, void* workspace,
+                                               int64_t ws_bytes, void* stream) {
+  IC2_CHECK_ARG(n >= 0 && k >= 1 && k <= 1024, "gumbel_softmax_quantize_bwd: need 1 <= k <= 1024 (k=%d)", k);
+  IC2_CHECK_ARG(n == 0 || (z && codebook && grad_disc && dz_out), "gumbel_softmax_quantize_bwd: null pointer");
+  IC2_CHECK_ARG(log_tau || tau > 0.f, "gumbel_softmax_quantize_bwd: temperature must be positive");
+  IC2_CHECK_ARG(seed_dev != nullptr || gumbel_noise != nullptr || n == 0,
+                "gumbel_softmax_quantize_bwd: seed_dev and gumbel_noise are both null");
+  const int64_t g = ic2::gumbel_grid(n);
+  IC2_CHECK_ARG(!dlogt_out || n == 0 || (workspace && ws_bytes >= g * (int64_t)sizeof(float)),
+                "gumbel_softmax_quantize_bwd: dlogt_out needs a workspace of %lld bytes (got %lld)",
+                (long long)(g * (int64_t)sizeof(float)), (long long)ws_bytes);
+  hipStream_t s = ic2::as_stream(stream);
+  if (n == 0) {
+    if (dlogt_out) {  // an empty batch: dlog tau = 0 (np = 0 reads nothing)
+      hipLaunchKernelGGL(ic2::gumbel_dlogt_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)nullptr, 0,
+                         dlogt_out);
+      IC2_CHECK_LAUNCH("gumbel_softmax_quantize_bwd");
+    }
+    return IC2_OK;
+  }
+  float* part = dlogt_out ? reinterpret_cast<float*>(workspace) : nullptr;
+  const uint64_t* sdv = reinterpret_cast<const uint64_t*>(seed_dev);
+#define IC2_GSB(KPL)                                                                                             \
+  hipLaunchKernelGGL(ic2::gumbel_softmax_bwd_kernel<KPL>, dim3((unsigned)g), dim3(256), 0, s, z, n, codebook, k, \
+                     log_tau, tau, sdv, offset, gumbel_noise, grad_disc, q, dz_out, part)
+  if (k <= 64) IC2_GSB(1);
+  else if (k <= 128) IC2_GSB(2);
+  else if (k <= 256) IC2_GSB(4);
+  else if (k <= 512) IC2_GSB(8);
+  else IC2_GSB(16);
+#undef IC2_GSB
+  IC2_CHECK_LAUNCH("gumbel_softmax_quantize_bwd");
+  if (dlogt_out) {
+    hipLaunchKernelGGL(ic2::gumbel_dlogt_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)part, (int)g,
+                       dlogt_out);
+    IC2_CHECK_LAUNCH("gumbel_softmax_quantize_bwd (dlog tau)");
+  }
+  return IC2_OK;
+}
+
+extern "C" int ic2_gumbel_noise(const int64_t* seed_dev, uint64_t seed, uint64_t offset, int64_t n, int k,
+                                float* noise_out, void* stream) {
+  IC2_CHECK_ARG(n >= 0 && k >= 1 && k <= 1024, "gumbel_noise: need n >= 0 and 1 <= k <= 1024 (n=%lld k=%d)",
+                (long long)n, k);
+  IC2_CHECK_ARG(n == 0 || noise_out, "gumbel_noise: null pointer");
+  if (n == 0) return IC2_OK;
+  const int64_t total = n * (int64_t)k;
+  int64_t g = ic2::ceil_div(total, 256);
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(ic2::gumbel_noise_kernel, dim3((unsigned)g), dim3(256), 0, ic2::as_stream(stream), seed,
+                     reinterpret_cast<const uint64_t*>(seed_dev), offset, total, noise_out);
+  IC2_CHECK_LAUNCH("gumbel_noise");
+  return IC2_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

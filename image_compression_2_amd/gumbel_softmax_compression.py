@@ -11,8 +11,12 @@ fc1 from -- advances exactly as the reference's.  The device generator's offset 
 the reference's [N*8192, K] exponential_ draw (only later device draws, e.g. the reparameterisation noise of w_plus,
 see that); compress()/decompress() are deterministic and bit-exact, and compress() skips the noise entirely (its
 indices are the exact argmin) while still counting `usage` in training mode as the reference's does.
-Forward is inference-only: it runs in grad mode, but a backward through the kernel raises (training is out of
-scope).
+Training (the reference's ``train_gumbel_discretized_hvae``, :322-611): in training mode (``compressor.train()``,
+:504) with grad mode on and ``z`` or ``log_temperature`` requiring grad, forward runs the same kernel under autograd
+(``autograd_ops.GumbelSoftmaxQuantize``): a HIP backward kernel gives dL/dz and dL/dlog_temperature through disc and
+the perplexity, soft or straight-through hard, with the probabilities recomputed from the saved seed.  The forward
+values and the ``usage`` update are the inference kernel's, bit for bit.  In eval mode forward stays inference-only:
+it runs in grad mode, but a backward through it raises ``AutogradUnsupported``.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nv
+from . import autograd_ops as ao
 from .stylegan3_hvae_full import HVAE_VGG_Encoder, StyleGAN3Compressor, save_tensor_as_image, resize_bilinear  # noqa: F401
 
 
@@ -89,9 +94,6 @@ class GumbelSoftmaxDiscretization(nn.Module):
         nv.require_gpu(z)
         m = z.numel()
         k = self.n_embeddings
-        disc = torch.empty(m, dtype=torch.float32, device=z.device)
-        idx = torch.empty(m, dtype=torch.int64, device=z.device)
-        psum = torch.zeros(k, dtype=torch.float32, device=z.device)
         if gumbel_noise is not None:
             gumbel_noise = gumbel_noise.to(torch.float32).contiguous()
             assert gumbel_noise.shape == (m, k)
@@ -100,17 +102,29 @@ class GumbelSoftmaxDiscretization(nn.Module):
         # fine projector re-creates fc1 on every encoder call (stylegan3_hvae_full.py:225-230) -- advances exactly as
         # the reference's does
         seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=z.device)
-        nv.call("ic2_gumbel_softmax_quantize_dseed", nv.ptr(z), m, nv.ptr(self.codebook), k,
-                nv.ptr(self.log_temperature.detach()), 1.0, int(bool(hard)), nv.ptr(seed), 0, nv.ptr(gumbel_noise),
-                nv.ptr(disc), nv.ptr(idx), nv.ptr(psum), nv.stream_of(z))
+        # training mode with a graph wanted (the reference's trainer, compressor.train() at :504 and loss.backward()
+        # at :562-566): the same kernel under autograd (ao.GumbelSoftmaxQuantize, HIP backward); same forward values
+        train_graph = self.training and bool(nv.grad_inputs((z_in, self.log_temperature)))
+        if train_graph:
+            disc, perplexity, idx = ao.GumbelSoftmaxQuantize.apply(z_in, self.log_temperature, self.codebook, seed,
+                                                                   bool(hard), gumbel_noise)
+        else:
+            disc = torch.empty(m, dtype=torch.float32, device=z.device)
+            idx = torch.empty(m, dtype=torch.int64, device=z.device)
+            psum = torch.zeros(k, dtype=torch.float32, device=z.device)
+            nv.call("ic2_gumbel_softmax_quantize_dseed", nv.ptr(z), m, nv.ptr(self.codebook), k,
+                    nv.ptr(self.log_temperature.detach()), 1.0, int(bool(hard)), nv.ptr(seed), 0, nv.ptr(gumbel_noise),
+                    nv.ptr(disc), nv.ptr(idx), nv.ptr(psum), nv.stream_of(z))
         if self.training:
             hist = torch.zeros(k, dtype=torch.int32, device=z.device)
             nv.call("ic2_quantize_codebook_argmin", nv.ptr(z), m, nv.ptr(self.codebook), k, nv.ptr(idx), None,
                     nv.ptr(hist), nv.stream_of(z))
             self.usage += hist.to(self.usage.dtype)
+        if train_graph:
+            return disc.view(batch_size, num_ws, w_dim), perplexity, idx
         avg_probs = psum / m
         perplexity = torch.exp(-torch.sum(avg_probs * torch.log(avg_probs + 1e-10)))
-        # inference in grad mode works; a backward through the fused kernel raises (training is out of scope)
+        # eval mode: inference in grad mode works; a backward through the inference kernel raises
         return nv.refuse_backward("GumbelSoftmaxDiscretization.forward", (disc.view(batch_size, num_ws, w_dim),
                                   perplexity, idx), (z_in, self.log_temperature))
 

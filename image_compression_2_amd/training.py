@@ -24,6 +24,10 @@ Deviations, all explicit:
     fine projector's fc1, which the reference re-creates from the CPU generator on every call (:225-230), is
     broadcast from rank 0 after each re-creation, so every rank runs -- and averages the gradients of -- the same
     weights (or build the encoder with fix_fine_projector=True: no re-creation at all).
+
+The reference's second trainer, ``train_gumbel_discretized_hvae`` (gumbel_softmax_compression.py:322-611), which also
+trains the quantizer's ``log_temperature`` through the Gumbel-softmax, is ``make_gumbel_optimizer`` +
+``train_step_gumbel`` below, with the same deviations.
 """
 from __future__ import annotations
 
@@ -150,3 +154,109 @@ def _train_step(compressor, encoder, images, optimizer, w_avg, rec_weight, perce
         optimizer.step()
     return {"rec_loss": rec_loss.detach(), "kl_loss": kl.detach(), "perceptual_loss": perceptual.detach(),
             "total_loss": loss.detach()}
+
+
+# ------------------------------------------------------------------------------------------------
+# The reference's second trainer: train_gumbel_discretized_hvae (gumbel_softmax_compression.py:322-611), which
+# trains the encoder and the quantizer's log_temperature through GumbelSoftmaxCompressor.forward (:172-200).
+# ------------------------------------------------------------------------------------------------
+def make_gumbel_optimizer(compressor, lr=1e-4):
+    """The reference's optimizer (gumbel_softmax_compression.py:414-418): Adam over the encoder's and the
+    discretization's parameters (``log_temperature``), fused on the device like make_optimizer's."""
+    params = list(compressor.encoder.parameters()) + list(compressor.discretization.parameters())
+    fused = all(p.is_cuda for p in params)
+    return torch.optim.Adam(params, lr=lr, betas=(0.9, 0.999), fused=fused or None)
+
+
+def train_step_gumbel(compressor, images, optimizer, w_avg, n_embeddings=None, rec_weight=1.0, perceptual_weight=0.8,
+                      kl_weight=0.01, gumbel_weight=1.0, percep=None, scaler=None, sync_gradients=None,
+                      shared_trunk=True):
+    """One optimisation step of the reference's Gumbel trainer (gumbel_softmax_compression.py:527-567) on a
+    GumbelSoftmaxCompressor in training mode (``compressor.train()``, :504); returns the five losses and the
+    perplexity as 0-d device tensors (no host sync).  Per batch, as the reference:
+
+        optimizer.zero_grad()                                                     :528
+        reconstructed, w_plus, w_discrete, perplexity = compressor(images)        :533  encoder -> means ->
+                                                        Gumbel-softmax quantizer (HIP fwd/bwd) -> frozen G.synthesis
+        rec_loss = F.mse_loss(images, reconstructed)                              :536
+        perceptual = percep(images, reconstructed).mean()                         :539
+        _, means, logvars = encoder(images); kl as train_step's                   :542-547
+        perplexity_loss = (perplexity - n_embeddings)^2                           :551-552
+        loss = rec_weight * rec + perceptual_weight * perceptual + kl_weight * kl
+               + gumbel_weight * perplexity_loss                                  :555-558
+        loss.backward(); optimizer.step()                                         :561-567
+
+    ``n_embeddings``: the ideal perplexity (the reference passes the codebook size, :332, :551); None = the
+    compressor's codebook size.  The temperature annealing stays the caller's ``discretization.update_temp``, once
+    per epoch (:579-582).  train_step's explicit deviations hold here too: ``percep`` is caller-supplied and a
+    non-zero ``perceptual_weight`` without it raises; the graph is always built (the reference's non-fp16 branch
+    runs under no_grad, :531, and cannot train); ``scaler`` is make_f16's GradScaler.  ``shared_trunk``: the two
+    encoder calls (:533, :542) share one trunk and run the heads twice, RNG draws in the reference's order: heads
+    (fc1 re-draw, reparameterisation noise) -> the quantizer's noise seed on the device -> synthesis -> heads.
+    Data parallel: the encoder's gradients go through its reducer as in train_step and the ``log_temperature``
+    gradient is averaged with distributed.allreduce_gradients; the perplexity (and its loss) and the ``usage``
+    counters are each rank's own batch's, as DistributedDataParallel around the reference's compressor would leave
+    them."""
+    if percep is None and perceptual_weight != 0:
+        raise ValueError("perceptual_weight != 0 needs a perceptual loss callable (the reference's LPIPS(net='vgg') "
+                         "weights are not available offline): pass percep=... or perceptual_weight=0")
+    disc = compressor.discretization
+    if not disc.training:
+        raise RuntimeError("train_step_gumbel needs the compressor in training mode (compressor.train(), as the "
+                           "reference's trainer, gumbel_softmax_compression.py:504): in eval mode the quantizer is "
+                           "inference-only")
+    encoder = compressor.encoder
+    if n_embeddings is None:
+        n_embeddings = disc.n_embeddings
+    optimizer.zero_grad()
+    world = sync_gradients if sync_gradients is not None else (
+        torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1)
+    projectors = (encoder.global_projector, encoder.medium_projector, encoder.fine_projector)
+    if world > 1:
+        for proj in projectors:
+            proj.fc1_hook = icd.broadcast_params
+    try:
+        return _train_step_gumbel(compressor, encoder, disc, images, optimizer, w_avg, float(n_embeddings),
+                                  rec_weight, perceptual_weight, kl_weight, gumbel_weight, percep, scaler,
+                                  sync_gradients, shared_trunk)
+    finally:
+        for proj in projectors:
+            proj.fc1_hook = None
+
+
+def _train_step_gumbel(compressor, encoder, disc, images, optimizer, w_avg, ideal_perplexity, rec_weight,
+                       perceptual_weight, kl_weight, gumbel_weight, percep, scaler, sync_gradients, shared_trunk):
+    with torch.enable_grad(), ao.derived_cache():
+        if shared_trunk:
+            pooled = encoder.trunk_train(images)
+            _, means_q, _ = encoder.heads_train(pooled)          # compressor(images): the encoder (:187) ...
+            w_discrete, perplexity, _ = disc(means_q)            # ... the quantizer on its means (:190) ...
+            reconstructed = _decode(compressor, w_discrete, images)   # ... the frozen synthesis (:193-198)
+            _, means, logvars = encoder.heads_train(pooled)      # encoder(images) (:542)
+        else:
+            reconstructed, _, _, perplexity = compressor(images)
+            _, means, logvars = encoder(images)
+        rec_loss = F.mse_loss(images, reconstructed)
+        perceptual = percep(images, reconstructed).mean() if percep is not None else rec_loss.new_zeros(())
+        kl = kl_divergence(means, logvars, w_avg)
+        # F.mse_loss(perplexity, tensor(n_embeddings)) of two 0-d tensors (:551-552), without the host -> device copy
+        perplexity_loss = (perplexity - ideal_perplexity) ** 2
+        loss = (rec_weight * rec_loss + perceptual_weight * perceptual + kl_weight * kl
+                + gumbel_weight * perplexity_loss)
+        reducer = _reducer(encoder, sync_gradients)
+        if reducer is not None:
+            reducer.start()
+        (scaler.scale(loss) if scaler is not None else loss).backward()
+    if reducer is not None:
+        reducer.finish()
+    else:
+        icd.allreduce_gradients(list(encoder.parameters()), sync_gradients)
+    icd.allreduce_gradients(list(disc.parameters()), sync_gradients)
+    if scaler is not None:
+        scaler.step(optimizer)
+        scaler.update()
+    else:
+        optimizer.step()
+    return {"rec_loss": rec_loss.detach(), "kl_loss": kl.detach(), "perceptual_loss": perceptual.detach(),
+            "perplexity_loss": perplexity_loss.detach(), "total_loss": loss.detach(),
+            "perplexity": perplexity.detach()}

@@ -97,6 +97,30 @@ int ic2_gumbel_softmax_quantize_dseed(const float* z, int64_t n, const float* co
                                       const float* gumbel_noise, float* disc_out, int64_t* idx_out,
                                       float* prob_sum_out, void* stream);
 
+/* Backward of ic2_gumbel_softmax_quantize_dseed: training through GumbelSoftmaxCompressor.forward
+ * (gumbel_softmax_compression.py:172-200; the step of train_gumbel_discretized_hvae, :527-567).  With a = the
+ * forward's y and p = softmax(a), recomputed per latent from the same noise -- gumbel_noise, or the Philox stream of
+ * the forward's (*seed_dev, offset); never stored:
+ *   r_k = grad_disc[i] * c_k + q[k];  da_k = p_k * (r_k - sum_j p_j * r_j);
+ *   dz_out[i] = -(1 / tau) * sum_k da_k * sign(z[i] - c_k)   (sign(0) = 0);
+ *   dlogt_out[0] (nullable) = -sum_i sum_k da_ik * a_ik   (the gradient w.r.t. log tau).
+ * grad_disc [n] = dL/d disc_out; q [k] (nullable = 0) = dL/d (column mean of ret), i.e. for the perplexity
+ * (:126-127) q_k = dL/dperp * perp * -(log(avg_k + 1e-10) + avg_k / (avg_k + 1e-10)) / n with avg = prob_sum / n.
+ * The hard mode's one-hot is detached (straight-through), so the gradient does not depend on `hard`.
+ * Deterministic, no atomics: dlogt_out needs a workspace of ic2_gumbel_softmax_bwd_ws_bytes(n) bytes (host-only
+ * query; one f32 partial per workgroup, summed in index order in f64 by a second kernel). */
+int64_t ic2_gumbel_softmax_bwd_ws_bytes(int64_t n);
+int ic2_gumbel_softmax_quantize_bwd(const float* z, int64_t n, const float* codebook, int k, const float* log_tau,
+                                    float tau, const int64_t* seed_dev, uint64_t offset, const float* gumbel_noise,
+                                    const float* grad_disc, const float* q, float* dz_out, float* dlogt_out,
+                                    void* workspace, int64_t ws_bytes, void* stream);
+
+/* The noise the fused Gumbel kernels draw: noise_out [n][k] f32, element (i, j) = -log(-log(u)) of the Philox4x32-10
+ * counter offset + i*k + j keyed by *seed_dev (device, when non-NULL) or `seed`.  Feeding it back as gumbel_noise
+ * reproduces the generated-noise results bit for bit (what makes the backward's replay testable). */
+int ic2_gumbel_noise(const int64_t* seed_dev, uint64_t seed, uint64_t offset, int64_t n, int k, float* noise_out,
+                     void* stream);
+
 /* Per-batch code record (SURVEY.md 8e metric record; usage / perplexity over the batch,
  * gumbel_softmax_compression.py:121-127): kind 0 = f32 latents from ic2_quantize_uniform at `bits` (code =
  * round((q + 1) * 0.5 * (2^bits - 1)), k = 2^bits), kind 1 = int64 codebook indices (k codes).  counts uint32 [k + 2],
