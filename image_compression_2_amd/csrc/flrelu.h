@@ -1,5 +1,5 @@
-// Shared between the fused filtered-lrelu kernels (flrelu.hip: VALU, every dtype/layout;
-// flrelu_mfma.hip: the bf16 NHWC synthesis path on MFMA).
+// Shared between the fused filtered-lrelu kernels (flrelu.hip: VALU, f32 / bf16, NCHW / NHWC;
+// flrelu_mfma.hip: MFMA, f16 (the synthesis path) or bf16 input, NHWC / NHWC16).
 #pragma once
 #include "common.h"
 
@@ -17,7 +17,6 @@ struct FlrArgs {
   int in_h, in_w, out_h, out_w;
   int py0, px0;                 // leading padding
   int tiles_x, tiles_y, cblocks, nimg;
-  int order;  // wide MFMA kernel: tile order, 0 = channel block fastest, 1 = x, y fastest (one plane per XCD run)
   int out_f16;  // MFMA kernels: output f16 (saturated) instead of bf16 (the synthesis's f16 mode)
   int out_blocked;  // strip MFMA kernel: output channel-blocked NHWC16 [n][c_p/16][out_h][out_w][16] instead of NHWC
   float slope, lim;  // lrelu slope (<= 1) and clamp bound / gain (+inf = no clamp)

@@ -3,6 +3,9 @@
 //   -> upfirdn2d(fd, down)]; called by SynthesisLayer.forward for every layer of
 // G.synthesis (/root/reference/stylegan3_hvae_full.py:274,329).
 //
+// This file holds the C entry points, the argument checks and the VALU kernel: f32 / bf16, NCHW / NHWC, with or
+// without a bias.  f16 input (the synthesis) and bias-free bf16 NHWC go to the MFMA kernels (flrelu_mfma.hip).
+//
 // One workgroup = one (sample, 16x16 output tile (NHWC bf16; 24x8 otherwise), 16-channel block).  Lanes own channel PAIRS
 // (packed fp32 math, bf16x2 loads), the spatial FIR runs from registers with every tap index
 // resolved at compile time (polyphase: zero-inserted samples are never multiplied), and the
@@ -239,68 +242,38 @@ __global__ void __launch_bounds__(FLR_THREADS) __attribute__((amdgpu_waves_per_e
 // ------------------------------------------------------------------------------------------------
 // dispatch
 // ------------------------------------------------------------------------------------------------
-// Tile geometries (TOY, TOX, channels per workgroup, threads).  The bf16 NHWC instances (the synthesis
-// throughput path) are tuned per up-factor; every other dtype/layout uses geometry 0 only.
-// IC2_FLR_VARIANT=k forces geometry k on the bf16 NHWC path (tuning, tools/bench_kernels.py).
-struct FlrGeomSel {
+// Tile (TOY, TOX, channels per workgroup, threads): bf16 NHWC runs 16x16 tiles (fastest on every SG3-T-256 layer
+// but the 36^2 ones, profiles/r1_flr_variants.txt), every other dtype / layout 24x8.
+struct FlrTile {
   int toy, tox, cpb, nt;
 };
-static const FlrGeomSel kFlrGeoms[] = {
-    {24, 8, 16, 256}, {16, 8, 16, 256}, {16, 16, 16, 256}, {8, 16, 16, 256}, {12, 16, 16, 256}, {16, 16, 8, 128}};
-constexpr int kNumFlrGeoms = sizeof(kFlrGeoms) / sizeof(kFlrGeoms[0]);
-static int flr_variant() {
-  static const int v = [] {
-    const int x = knob("IC2_FLR_VARIANT", -1);
-    return (x >= 0 && x < kNumFlrGeoms) ? x : -1;
-  }();
-  return v;
-}
-static int flr_pick(bool tuned, int up) {
-  if (!tuned) return 0;
-  if (flr_variant() >= 0) return flr_variant();
-  (void)up;
-  return 2;  // 16x16 tiles: fastest on every SG3-T-256 layer but the 36^2 ones (profiles/r1_flr_variants.txt)
-}
+constexpr FlrTile flr_tile(bool bf16_nhwc) { return bf16_nhwc ? FlrTile{16, 16, 16, 256} : FlrTile{24, 8, 16, 256}; }
 
 template <typename TI, typename TO, bool CHLAST, int U, int D, int TU, int TD, int DL>
-static int launch_geom(const FlrArgs& a, int geom, int grid, hipStream_t s) {
-#define IC2_FLR_LAUNCH(TY, TX, CPB, NT)                                                                            \
-  hipLaunchKernelGGL((flrelu_kernel<TI, TO, CHLAST, U, D, TU, TD, DL, TY, TX, CPB, NT>), dim3(grid), dim3(NT), 0, s, a)
-  constexpr bool tuned = CHLAST && std::is_same<TI, bf16_t>::value;
-  if constexpr (tuned) {
-    switch (geom) {
-      case 1: IC2_FLR_LAUNCH(16, 8, 16, 256); return IC2_OK;
-      case 2: IC2_FLR_LAUNCH(16, 16, 16, 256); return IC2_OK;
-      case 3: IC2_FLR_LAUNCH(8, 16, 16, 256); return IC2_OK;
-      case 4: IC2_FLR_LAUNCH(12, 16, 16, 256); return IC2_OK;
-      case 5: IC2_FLR_LAUNCH(16, 16, 8, 128); return IC2_OK;
-      default: break;
-    }
-  }
-  if (geom != 0) return IC2_E_UNSUPPORTED;
-  IC2_FLR_LAUNCH(24, 8, 16, 256);
+static int launch_geom(const FlrArgs& a, int grid, hipStream_t s) {
+  constexpr FlrTile T = flr_tile(CHLAST && std::is_same<TI, bf16_t>::value);
+  hipLaunchKernelGGL((flrelu_kernel<TI, TO, CHLAST, U, D, TU, TD, DL, T.toy, T.tox, T.cpb, T.nt>), dim3(grid),
+                     dim3(T.nt), 0, s, a);
   return IC2_OK;
-#undef IC2_FLR_LAUNCH
 }
 
 template <typename TI, typename TO, bool CHLAST, int U, int D, int TU, int TD>
-static int launch_delta(const FlrArgs& a, int delta, int geom, int grid, hipStream_t s) {
+static int launch_delta(const FlrArgs& a, int delta, int grid, hipStream_t s) {
   switch (delta) {
-    case 0: return launch_geom<TI, TO, CHLAST, U, D, TU, TD, 0>(a, geom, grid, s);
-    case 1: return launch_geom<TI, TO, CHLAST, U, D, TU, TD, 1>(a, geom, grid, s);
-    case 2: if constexpr (U > 2) return launch_geom<TI, TO, CHLAST, U, D, TU, TD, 2>(a, geom, grid, s); break;
-    case 3: if constexpr (U > 3) return launch_geom<TI, TO, CHLAST, U, D, TU, TD, 3>(a, geom, grid, s); break;
+    case 0: return launch_geom<TI, TO, CHLAST, U, D, TU, TD, 0>(a, grid, s);
+    case 1: return launch_geom<TI, TO, CHLAST, U, D, TU, TD, 1>(a, grid, s);
+    case 2: if constexpr (U > 2) return launch_geom<TI, TO, CHLAST, U, D, TU, TD, 2>(a, grid, s); break;
+    case 3: if constexpr (U > 3) return launch_geom<TI, TO, CHLAST, U, D, TU, TD, 3>(a, grid, s); break;
   }
   return IC2_E_UNSUPPORTED;
 }
 
 template <typename TI, typename TO, bool CHLAST>
-static int launch_cfg(const FlrArgs& a, int up, int down, int tu, int td, int delta, int geom, int grid,
-                      hipStream_t s) {
+static int launch_cfg(const FlrArgs& a, int up, int down, int tu, int td, int delta, int grid, hipStream_t s) {
   if (up == 2 && down == 2 && tu == 12 && td == 12)
-    return launch_delta<TI, TO, CHLAST, 2, 2, 12, 12>(a, delta, geom, grid, s);
+    return launch_delta<TI, TO, CHLAST, 2, 2, 12, 12>(a, delta, grid, s);
   if (up == 4 && down == 2 && tu == 24 && td == 12)
-    return launch_delta<TI, TO, CHLAST, 4, 2, 24, 12>(a, delta, geom, grid, s);
+    return launch_delta<TI, TO, CHLAST, 4, 2, 24, 12>(a, delta, grid, s);
   return IC2_E_UNSUPPORTED;
 }
 
@@ -390,8 +363,8 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
   a.in_h = in_h; a.in_w = in_w; a.out_h = out_h; a.out_w = out_w;
   a.py0 = py0; a.px0 = px0;
   hipStream_t s = as_stream(stream);
-  // bf16 NHWC (the synthesis throughput path): the MFMA formulation (flrelu_mfma.hip) unless
-  // knob IC2_FLR_MFMA=0 asks for the VALU kernel below
+  // bf16 NHWC without a bias: the MFMA formulation (flrelu_mfma.hip) unless knob IC2_FLR_MFMA=0 asks for
+  // the VALU kernel below
   static const bool use_mfma = knob("IC2_FLR_MFMA", 1) != 0;
   // f16 input (the synthesis conv epilogue's output) exists only for the MFMA formulation
   // (one polyphase phase for both axes: the instances take a single delta)
@@ -440,8 +413,7 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
               name);
     return IC2_E_UNSUPPORTED;
   }
-  const int geom = flr_pick(chlast && dtype_in == IC2_BF16 && dtype_out == IC2_BF16, up);
-  const FlrGeomSel fv = kFlrGeoms[geom];
+  const FlrTile fv = flr_tile(chlast && dtype_in == IC2_BF16 && dtype_out == IC2_BF16);
   a.tiles_x = (int)ceil_div(out_w, fv.tox);
   a.tiles_y = (int)ceil_div(out_h, fv.toy);
   a.cblocks = (int)ceil_div(a.c, fv.cpb);
@@ -458,11 +430,11 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
   IC2_CHECK_ARG(grid < (1LL << 31), "%s: grid too large", name);
   int rc;
   if (dtype_in == IC2_BF16 && dtype_out == IC2_BF16)
-    rc = chlast ? launch_cfg<bf16_t, bf16_t, true>(a, up, down, fu_taps, fd_taps, dx, geom, (int)grid, s)
-                : launch_cfg<bf16_t, bf16_t, false>(a, up, down, fu_taps, fd_taps, dx, geom, (int)grid, s);
+    rc = chlast ? launch_cfg<bf16_t, bf16_t, true>(a, up, down, fu_taps, fd_taps, dx, (int)grid, s)
+                : launch_cfg<bf16_t, bf16_t, false>(a, up, down, fu_taps, fd_taps, dx, (int)grid, s);
   else if (dtype_in == IC2_F32 && dtype_out == IC2_F32)
-    rc = chlast ? launch_cfg<float, float, true>(a, up, down, fu_taps, fd_taps, dx, geom, (int)grid, s)
-                : launch_cfg<float, float, false>(a, up, down, fu_taps, fd_taps, dx, geom, (int)grid, s);
+    rc = chlast ? launch_cfg<float, float, true>(a, up, down, fu_taps, fd_taps, dx, (int)grid, s)
+                : launch_cfg<float, float, false>(a, up, down, fu_taps, fd_taps, dx, (int)grid, s);
   else {
     set_error("%s: unsupported dtype pair %d -> %d", name, dtype_in, dtype_out);
     return IC2_E_INVALID;

@@ -295,10 +295,16 @@ static void fb_launch(const FlrBwdArgs& a, int ti, int tg, int grid, hipStream_t
 
 using namespace ic2;
 
+// the gx tile (FB_TILE x FB_TILE: fastest on every SG3-T-256 layer, profiles/r2_flr_bwd_variants.txt); one ydot
+// partial per tile and channel
+constexpr int FB_TILE = 16;
+static int64_t fb_ydot_floats(int n, int c_p, int in_h, int in_w) {
+  return (int64_t)n * ceil_div(in_h, FB_TILE) * ceil_div(in_w, FB_TILE) * c_p;
+}
+
 extern "C" int64_t ic2_flrelu_bwd_ydot_floats(int n, int c_p, int in_h, int in_w, int up) {
-  const int tiy = 16, tix = 16;  // the default tile variant
   (void)up;
-  return (int64_t)n * ceil_div(in_h, tiy) * ceil_div(in_w, tix) * c_p;
+  return fb_ydot_floats(n, c_p, in_h, in_w);
 }
 
 extern "C" int ic2_flrelu_bwd_nhwc_ex(const void* x, int x_dtype, const void* gout, int g_dtype, void* gx,
@@ -343,8 +349,8 @@ extern "C" int ic2_flrelu_bwd_nhwc_ex(const void* x, int x_dtype, const void* go
   // IC2_FLRB_MFMA=0; ydot from the stored gx there
   static const bool mfma = knob("IC2_FLRB_MFMA", 1) != 0;
   const bool gf16 = g_dtype == IC2_F16;
+  const int64_t need = fb_ydot_floats(n, c_p, in_h, in_w);
   if ((mfma || gf16) && x_dtype == IC2_F16 && ((g_dtype == IC2_BF16 && gx_dtype == IC2_BF16) || gf16)) {
-    const int64_t need = (int64_t)n * ceil_div(in_h, 16) * ceil_div(in_w, 16) * c_p;
     IC2_CHECK_ARG(ydot == nullptr || ydot_floats >= need, "flrelu_bwd_nhwc: ydot needs %lld floats", (long long)need);
     // U is recomputed with f16 taps rounded as the forward rounds its vertical taps (joint per-phase rounding, ADVICE
     // r3), so the lrelu side is decided on the forward's operands.  With a finite clamp the forward's horizontal up pass
@@ -366,37 +372,22 @@ extern "C" int ic2_flrelu_bwd_nhwc_ex(const void* x, int x_dtype, const void* go
   const int q = px0 - fu_taps + 1 - fd_taps + 1;
   const int ph = ((-q) % down + down) % down;
   const int R = fd_taps - 1 - ph;
-  // tile variants (TIY, TIX, channel pairs, threads); knob IC2_FLRB_VARIANT=k picks one (tuning, tools/bench_flr_bwd.py)
-  static const int variant = knob("IC2_FLRB_VARIANT", -1);
-  const int v = variant >= 0 ? variant : 1;   // 16x16 tiles: fastest on every SG3-T-256 layer (profiles/r2_flr_bwd_variants.txt)
-  int tiy, tix, np;
-  if (v == 1) { tiy = 16; tix = 16; np = cfg2 ? 2 : 1; }
-  else if (v == 2) { tiy = 8; tix = 16; np = cfg2 ? 2 : 1; }
-  else { tiy = cfg2 ? 8 : 4; tix = cfg2 ? 16 : 8; np = 4; }
-  a.tiles_x = (int)ceil_div(in_w, tix);
-  a.tiles_y = (int)ceil_div(in_h, tiy);
+  const int np = cfg2 ? 2 : 1;  // channel pairs per workgroup
+  a.tiles_x = (int)ceil_div(in_w, FB_TILE);
+  a.tiles_y = (int)ceil_div(in_h, FB_TILE);
   IC2_CHECK_ARG(c_p % (2 * np) == 0, "flrelu_bwd_nhwc: c_p must be a multiple of %d", 2 * np);
   a.cblocks = c_p / (2 * np);
   const int64_t grid = (int64_t)n * a.tiles_y * a.tiles_x * a.cblocks;
   IC2_CHECK_ARG(grid < (1LL << 31), "flrelu_bwd_nhwc: grid too large");
-  IC2_CHECK_ARG(ydot == nullptr || (v == 1 && ydot_floats >= (int64_t)n * a.tiles_y * a.tiles_x * c_p),
-                "flrelu_bwd_nhwc: ydot needs the default tiles and %lld floats",
-                (long long)((int64_t)n * a.tiles_y * a.tiles_x * c_p));
+  IC2_CHECK_ARG(ydot == nullptr || ydot_floats >= need, "flrelu_bwd_nhwc: ydot needs %lld floats", (long long)need);
   hipStream_t s = as_stream(stream);
-#define IC2_FB_R(U_, TU_, TIY_, TIX_, NP_, NT_)                                                     \
-  do {                                                                                              \
-    if (R == 11) fb_launch<U_, 2, TU_, 12, 11, TIY_, TIX_, NP_, NT_>(a, x_dtype, g_dtype, (int)grid, s); \
-    else fb_launch<U_, 2, TU_, 12, 10, TIY_, TIX_, NP_, NT_>(a, x_dtype, g_dtype, (int)grid, s);         \
+#define IC2_FB_R(U_, TU_, NP_)                                                                                  \
+  do {                                                                                                          \
+    if (R == 11) fb_launch<U_, 2, TU_, 12, 11, FB_TILE, FB_TILE, NP_, 128>(a, x_dtype, g_dtype, (int)grid, s); \
+    else fb_launch<U_, 2, TU_, 12, 10, FB_TILE, FB_TILE, NP_, 128>(a, x_dtype, g_dtype, (int)grid, s);         \
   } while (0)
-  if (cfg2) {
-    if (v == 1) IC2_FB_R(2, 12, 16, 16, 2, 128);
-    else if (v == 2) IC2_FB_R(2, 12, 8, 16, 2, 64);
-    else IC2_FB_R(2, 12, 8, 16, 4, 128);
-  } else {
-    if (v == 1) IC2_FB_R(4, 24, 16, 16, 1, 128);
-    else if (v == 2) IC2_FB_R(4, 24, 8, 16, 1, 64);
-    else IC2_FB_R(4, 24, 4, 8, 4, 128);
-  }
+  if (cfg2) IC2_FB_R(2, 12, 2);
+  else IC2_FB_R(4, 24, 1);
 #undef IC2_FB_R
   IC2_CHECK_LAUNCH("flrelu_bwd_nhwc");
   return IC2_OK;

@@ -101,40 +101,14 @@ __device__ __forceinline__ float fb_dact(float u, float ga, float slope, float g
   return l < lim ? ga * gs : 0.f;
 }
 
-// the item's oscale row: 1 (default) = DMA'd into a 64-B LDS slot by four lanes of the last wave with the ring groups,
-// as the forward strip kernel DMAs its post-scale row (flrelu_mfma.hip flrelu_mfma3_kernel ps_lds), retired by the
-// item-top vmcnt + barrier; 0 = a plain global load per lane and a vmcnt(0) at the item top.  (Round 3 fell back to 0
-// after wrong rows; the cause was fm_dma16's missing wait states, flrelu_mfma.h; 2 = the diagnostic build that found it)
-#ifndef FBM_OS_DMA
-#define FBM_OS_DMA 1
-#endif
-#if FBM_OS_DMA == 2
-// diagnostic (FBM_OS_DMA=2): the DMA'd row is checked against a plain load of the same row; mismatches are counted
-// per (first item / later item), per wave, and the first one is described (item, wave, lane, got, want, and whether the
-// value read is the previous item's row)
-// g_fbm_dbg[63] is the mode: bit 0 = at the DMA's issue (block kend of the previous item) wave NW-1 waits for it and
-// checks the slot itself ([5] good, [6] bad there); [42..57] the slot's 16 dwords at the first bad read, [58..61] the
-// first LDS dword indices (of this workgroup's allocation) holding the expected value's bits, [62] the item the slot's
-// last DMA was issued for (recorded in LDS by the issuing lane)
-__device__ unsigned int g_fbm_dbg[64];
-extern "C" int ic2_fbm_debug_fetch(unsigned int* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fbm_dbg), sizeof(g_fbm_dbg), 0, hipMemcpyDeviceToHost);
-}
-extern "C" int ic2_fbm_debug_reset(unsigned int mode) {
-  unsigned int z[64] = {};
-  z[63] = mode;
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_fbm_dbg), z, sizeof(z), 0, hipMemcpyHostToDevice);
-}
-#endif
-
 template <int U, int TJX, bool GF16>
 __global__ void __launch_bounds__(512, 4) flrelu_bwd_mfma_kernel(FlrBwdMArgs a, int nitems, int nseg, int seg_len) {
   using G = FbmGeom<U, TJX>;
   constexpr int NW = G::NW, NT = 64 * NW, NBT = G::NBT, NBX = G::NBX, NINX = G::NINX, NOX = G::NOX, S = G::S;
   constexpr int OCW = G::OCW, NGX = G::NGX;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[G::LDS_DW + (FBM_OS_DMA ? (FBM_OS_DMA == 2 ? 32 : 16) : 0)];
+  __shared__ __attribute__((aligned(16))) uint32_t lds[G::LDS_DW + 16];
   uint32_t* const xring = lds;
-  uint32_t* const os_lds = lds + G::LDS_DW;  // FBM_OS_DMA: the item's oscale row (its own slot)
+  uint32_t* const os_lds = lds + G::LDS_DW;  // the item's 16 oscale floats (their own slot)
   uint32_t* const gring = lds + G::XR_DW;
   uint32_t* const v_img = gring + G::GR_DW;  // V (f16), then P (bf16) row by row
   uint32_t* const a_img = v_img + G::V_DW;   // GAv (bf16)
@@ -234,19 +208,12 @@ __global__ void __launch_bounds__(512, 4) flrelu_bwd_mfma_kernel(FlrBwdMArgs a, 
     for (int q = 0; q < NGX; ++q) load_xgroup(n, o.iy0, o.ix0, c0, q);
 #pragma unroll
     for (int q = 0; q < 3; ++q) load_ggroup(n, o.oy0, o.ox0, c0, q);
-    if (FBM_OS_DMA && a.oscale != nullptr && wave == NW - 1 && lane < 4) {  // 64 B: oscale[n][c0 .. c0 + 16)
+    // the item's oscale row, 64 B = oscale[n][c0 .. c0 + 16): DMA'd into its own LDS slot by four lanes of the last
+    // wave, as the forward strip kernel DMAs its post-scale row (flrelu_mfma.hip flrelu_mfma3_kernel ps_lds)
+    if (a.oscale != nullptr && wave == NW - 1 && lane < 4) {
       const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
           (void*)(a.oscale + (int64_t)n * a.c_p + c0), 0, 64, 0x00020000);
       fm_dma16(prs, lane * 16, os_lds);
-#if FBM_OS_DMA == 2
-      if (lane == 0) os_lds[16] = (uint32_t)w;
-      if (g_fbm_dbg[63] & 1u) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const float want = a.oscale[(int64_t)n * a.c_p + c0 + 4 * lane];
-        const uint32_t got = os_lds[4 * lane];
-        atomicAdd(&g_fbm_dbg[got == __float_as_uint(want) ? 5 : 6], 1u);
-      }
-#endif
     }
   };
   if (slot < nitems) load_item(slot);
@@ -288,63 +255,18 @@ __global__ void __launch_bounds__(512, 4) flrelu_bwd_mfma_kernel(FlrBwdMArgs a, 
   __syncthreads();  // every wave's tap reads are done before the first GAv store overwrites the table
 
   bool first = true;
-#if FBM_OS_DMA == 2
-  int prev_w = -1;
-#endif
   for (int w = slot; w < nitems; w += gridDim.x) {
     int n, jx0, c0, t0, nt;
     item_geom(w, n, jx0, c0, t0, nt);
     const Org o = origin(jx0, t0);
     const bool has_next = w + (int)gridDim.x < nitems;
-#if FBM_OS_DMA == 2
-    const bool first_item = first;
-#endif
     if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OCW) : "memory");  // the previous item's last stores stay in flight
     first = false;
     __syncthreads();
-    // the item's oscale[n][c0 + 4g .. +3], retired here with a waitcnt the compiler accounts for (its own wait would
-    // land at the first tile's epilogue, behind the ring DMAs issued by then)
+    // the item's oscale[n][c0 + 4g .. +3]: landed with the ring groups (the wait + barrier above)
     float4 osv = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (a.oscale) {
-      if (FBM_OS_DMA) {
-        osv = *reinterpret_cast<const float4*>(os_lds + 4 * g);  // landed: the wait + barrier above
-#if FBM_OS_DMA == 2
-        const float4 ref = *reinterpret_cast<const float4*>(a.oscale + (int64_t)n * a.c_p + c0 + 4 * g);
-        const float* rp = &ref.x;
-        const float* gp = &osv.x;
-        bool bad = false;
-        for (int j = 0; j < 4; ++j) bad |= __float_as_uint(rp[j]) != __float_as_uint(gp[j]);
-        if (bad) {
-          atomicAdd(&g_fbm_dbg[0], 1u);
-          atomicAdd(&g_fbm_dbg[first_item ? 1 : 2], 1u);
-          atomicAdd(&g_fbm_dbg[8 + wave], 1u);
-          atomicAdd(&g_fbm_dbg[16 + g], 1u);
-          if (prev_w >= 0) {  // is it the previous item's row?
-            int pn, pj, pc, pt, pnt;
-            item_geom(prev_w, pn, pj, pc, pt, pnt);
-            const float4 pv = *reinterpret_cast<const float4*>(a.oscale + (int64_t)pn * a.c_p + pc + 4 * g);
-            if (__float_as_uint(pv.x) == __float_as_uint(osv.x)) atomicAdd(&g_fbm_dbg[3], 1u);
-          }
-          if (atomicCAS(&g_fbm_dbg[32], 0u, 1u) == 0u) {
-            g_fbm_dbg[33] = (unsigned)w; g_fbm_dbg[34] = (unsigned)wave; g_fbm_dbg[35] = (unsigned)lane;
-            g_fbm_dbg[36] = __float_as_uint(osv.x); g_fbm_dbg[37] = __float_as_uint(ref.x);
-            g_fbm_dbg[38] = (unsigned)prev_w; g_fbm_dbg[39] = (unsigned)blockIdx.x;
-            g_fbm_dbg[40] = (unsigned)nitems; g_fbm_dbg[41] = (unsigned)gridDim.x;
-            for (int j = 0; j < 16; ++j) g_fbm_dbg[42 + j] = os_lds[j];
-            int hits = 0;
-            for (int j = 0; j < G::LDS_DW + 16 && hits < 4; ++j)
-              if (lds[j] == __float_as_uint(ref.x)) g_fbm_dbg[58 + hits++] = (unsigned)j;
-            g_fbm_dbg[62] = os_lds[16];
-          }
-        }
-        atomicAdd(&g_fbm_dbg[4], 1u);  // rows read
-#endif
-      } else {
-        osv = *reinterpret_cast<const float4*>(a.oscale + (int64_t)n * a.c_p + c0 + 4 * g);
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-      }
-    }
+    if (a.oscale) osv = *reinterpret_cast<const float4*>(os_lds + 4 * g);
     const float osc[4] = {osv.x, osv.y, osv.z, osv.w};
     const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(gxo + (int64_t)n * a.in_h * xsy + c0), 0, FM_OOB, 0x00020000);
@@ -492,9 +414,6 @@ __global__ void __launch_bounds__(512, 4) flrelu_bwd_mfma_kernel(FlrBwdMArgs a, 
         if (U * t1 + 3 <= kend) block(U * t1 + 3, t1, std::integral_constant<int, 3>{});
       }
     }
-#if FBM_OS_DMA == 2
-    prev_w = w;
-#endif
   }
 }
 
@@ -503,23 +422,12 @@ static void fbm_launch(FlrBwdMArgs a, int n, hipStream_t s) {
   a.tiles_x = (int)ceil_div(a.in_w, TJX);
   a.tiles_y = (int)ceil_div(a.in_h, 16);
   a.cblocks = a.c_p / 16;
-  static int resident = 0;
-  if (resident == 0) {
-    int dev = 0, cus = 0, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, flrelu_bwd_mfma_kernel<U, TJX, GF16>, 512, 0);
-    resident = (cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 1);
-  }
+  static const int resident = fm_resident(flrelu_bwd_mfma_kernel<U, TJX, GF16>, 512);
   // strip segmentation as the forward's (fm_strip_segments); knob IC2_FLRB_SEGS=0 keeps the round-3 rule
   static const int segs_mode = knob("IC2_FLRB_SEGS", 1);
-  const int64_t nstrips = (int64_t)n * a.tiles_x * a.cblocks;
-  int nseg = fm_strip_segments(nstrips, a.tiles_y, resident, segs_mode == 1);
-  const int seg_len = (int)ceil_div(a.tiles_y, nseg);
-  nseg = (int)ceil_div(a.tiles_y, seg_len);
-  const int nitems = (int)(nstrips * nseg);
-  const int grid = nitems < resident ? nitems : resident;
-  hipLaunchKernelGGL((flrelu_bwd_mfma_kernel<U, TJX, GF16>), dim3((unsigned)grid), dim3(512), 0, s, a, nitems, nseg, seg_len);
+  const FmStripGrid sg = fm_strip_grid((int64_t)n * a.tiles_x * a.cblocks, a.tiles_y, resident, segs_mode == 1);
+  hipLaunchKernelGGL((flrelu_bwd_mfma_kernel<U, TJX, GF16>), dim3((unsigned)sg.grid), dim3(512), 0, s, a, sg.nitems,
+                     sg.nseg, sg.seg_len);
 }
 
 // per (sample, pixel chunk, channel) sums of gx * (x - bias) = dc * (x - bias) / oscale: the modulated conv's

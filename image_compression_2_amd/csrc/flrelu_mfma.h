@@ -10,12 +10,11 @@ typedef _Float16 fm_h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 fm_h8 __attribute__((ext_vector_type(8)));
 typedef short fm_s4 __attribute__((ext_vector_type(4)));
 typedef float fm_f4 __attribute__((ext_vector_type(4)));
-typedef float fm_f2 __attribute__((ext_vector_type(2)));
 typedef uint32_t v2u32_t __attribute__((ext_vector_type(2)));
 typedef uint32_t v4u32_t __attribute__((ext_vector_type(4)));
 
 constexpr int FM_TAPS = 276;
-// the wide / strip kernels' table also holds the clamp-split horizontal taps: guh at [328, 352), gdgl at [428, 440)
+// the strip kernel's table also holds the clamp-split horizontal taps: guh at [328, 352), gdgl at [428, 440)
 // (zero guards around each: the tap reads reach 15 below and 63 above gu's base, 30 below and 47 above gdg's)
 constexpr int FM_TAPS_CL = 476;
 constexpr uint32_t FM_OOB = 0x7ffffff0u;  // buffer num_records = the zero-answer offset (per-sample image < 2 GiB)
@@ -78,6 +77,31 @@ inline int fm_strip_segments(int64_t nstrips, int tiles_y, int resident, bool tu
     nseg = pick;
   }
   return (int)nseg;
+}
+
+// The launch of a persistent strip kernel: the segmentation above, evened out (nseg segments of seg_len tiles, the
+// last one shorter), the item count and the grid that takes them.
+struct FmStripGrid {
+  int nseg, seg_len, nitems, grid;
+};
+inline FmStripGrid fm_strip_grid(int64_t nstrips, int tiles_y, int resident, bool tune) {
+  FmStripGrid sg;
+  sg.seg_len = (int)ceil_div(tiles_y, fm_strip_segments(nstrips, tiles_y, resident, tune));
+  sg.nseg = (int)ceil_div(tiles_y, sg.seg_len);
+  sg.nitems = (int)(nstrips * sg.nseg);
+  sg.grid = sg.nitems < resident ? sg.nitems : resident;
+  return sg;
+}
+
+// Resident workgroups of a persistent kernel: every CU filled to the kernel's occupancy.  Queries the device, so a
+// launcher keeps the result in a function-local static of its kernel instance (one query per kernel, not per launch).
+template <typename K>
+inline int fm_resident(K kernel, int threads) {
+  int dev = 0, cus = 0, per_cu = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0);
+  return (cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 1);
 }
 
 }  // namespace ic2

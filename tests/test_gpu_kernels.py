@@ -185,6 +185,40 @@ def test_filtered_lrelu_nchw(cuda, case, dtype):
     assert _maxdiff(y, r) < tol * (1 + r.abs().max().item())
 
 
+@pytest.mark.parametrize("case", range(3))
+def test_flrelu_nhwc_bf16_bias(cuda, case):
+    """ic2_flrelu_nhwc with bf16 input, bf16 output and a bias.  The bias keeps the call off the MFMA kernels, so it
+    runs the VALU kernel on the bf16 NHWC tile (16x16), which no other test reaches: up 2 / up 4, positive and
+    negative padding, outputs that are no multiple of the tile.  Against the fp64 reference composition on the
+    bf16-rounded input, at test_filtered_lrelu_nchw's bf16 bar (same kernel template); the NaN pre-fill shows every
+    output element is written."""
+    import ctypes
+    up, down, tu, td, pad, s = FLR_CASES[case]
+    n, c_p = 2, 32
+    g = torch.Generator().manual_seed(30 + case)
+    x = (torch.randn(n, c_p, s, s, generator=g) * 3).bfloat16()
+    b = torch.randn(c_p, generator=g)
+    fu = sg3.design_lowpass_filter(tu, 8.0, 4.0, 64)
+    fd = sg3.design_lowpass_filter(td, 8.0, 4.0, 64)
+    so = (s * up + pad[0] + pad[1] - (tu - 1) - (td - 1) + (down - 1)) // down
+    xd = x.permute(0, 2, 3, 1).contiguous().to(cuda)
+    bd = b.to(cuda)
+    out = torch.full((n, so, so, c_p), float("nan"), device=cuda, dtype=torch.bfloat16)
+    fun, fdn = fu.float().contiguous().numpy(), fd.float().contiguous().numpy()
+    nv.call("ic2_flrelu_nhwc", nv.ptr(xd), nv.ptr(out), nv.BF16, nv.BF16, n, c_p, s, s, so, so,
+            fun.ctypes.data_as(ctypes.c_void_p), tu, fdn.ctypes.data_as(ctypes.c_void_p), td, nv.ptr(bd), up, down, *pad,
+            float(np.sqrt(2)), 0.2, 5.0, 0, None, nv.stream_of(xd))
+    torch.cuda.synchronize()
+    r = sg3.filtered_lrelu(x.double(), fu.double(), fd.double(), b.double(), up=up, down=down, padding=pad,
+                           gain=np.sqrt(2), slope=0.2, clamp=5.0)
+    y = out.float().cpu().permute(0, 3, 1, 2)
+    assert y.shape == r.shape
+    assert torch.isfinite(y).all()
+    d = _maxdiff(y, r)
+    print(f"max|diff| {d:.3e}  max|ref| {r.abs().max().item():.3e}")
+    assert d < 3e-2 * (1 + r.abs().max().item())
+
+
 # ------------------------------------------------------------------ fused FLR, synthesis (NHWC) path
 @pytest.fixture(scope="module")
 def gen256_bf16_layers():

@@ -88,16 +88,15 @@ def test_round2_entry_points_validate_before_launch():
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
-@pytest.mark.parametrize("os_dma", [0, 1])
-def test_lds_dma_wait_states(os_dma):
+def test_lds_dma_wait_states():
     """Every asm LDS-DMA of the strip kernels (fm_dma16) has the wait states the hardware needs in front of it: 5 after
     a VALU write of a descriptor SGPR, 1 after the SALU write of M0 (round-3 oscale-row failures: a spilled descriptor
-    restored by v_readlane one instruction before the DMA).  Audited on the gfx950 assembly by tools/audit_lds_dma.py,
-    for the production build and the backward's oscale-row DMA (FBM_OS_DMA)."""
+    restored by v_readlane one instruction before the DMA).  Audited on the gfx950 assembly by tools/audit_lds_dma.py;
+    the backward's oscale-row DMA is part of the one build there is."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "audit_lds_dma.py"), f"-DFBM_OS_DMA={os_dma}"],
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "audit_lds_dma.py")],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert " 0 short of wait states" in r.stdout

@@ -1,7 +1,6 @@
 """Per-layer timing of the fused filtered lrelu on the C2 shapes (SG3-T-256, batch 32, f16 NHWC16 in, bf16 out),
-HIP events around 20 back-to-back calls per layer.  python tools/ab_flr.py [label [res [n [blocked]]]]  (A/B: run once
-with IC2_DEV=1 IC2_FLR_STRIP=0 for the round-2 tile kernel; a fourth argument `blocked` asks for the channel-blocked
-NHWC16 output of the filtered lrelu -> conv hand-off)"""
+HIP events around 20 back-to-back calls per layer.  python tools/ab_flr.py [label [res [n [blocked]]]]  (a fourth
+argument `blocked` asks for the channel-blocked NHWC16 output of the filtered lrelu -> conv hand-off)"""
 import ctypes
 import os
 import sys

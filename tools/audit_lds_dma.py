@@ -2,7 +2,7 @@
 gfx950 assembly and, for every `buffer_load_dwordx4 ... lds`, counts the wait states since the last VALU write of an
 SGPR the DMA reads (descriptor, soffset: 5 needed) and since the last SALU write of M0 (1 needed).  The compiler pads
 these for a builtin but not around an asm statement, so the statement carries its own s_nop; this checks it does.
-    python tools/audit_lds_dma.py [-DFBM_OS_DMA=1 ...]     (exit 1 when a DMA is short of wait states)"""
+    python tools/audit_lds_dma.py [-DNAME=VALUE ...]     (exit 1 when a DMA is short of wait states)"""
 import os
 import re
 import subprocess

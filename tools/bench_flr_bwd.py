@@ -1,6 +1,6 @@
 """Per-layer timing of the fused filtered-lrelu backward (ic2_flrelu_bwd_nhwc) on the SG3-T-256 layers at the
-C5 batch, bf16 mode (f16 input, bf16 output gradient).  IC2_FLRB_VARIANT selects the tile variant (read once
-per process).  Prints one JSON line: per-layer ms and a checksum of the gradients."""
+C5 batch, bf16 mode (f16 input, bf16 output gradient).  Prints one JSON line: per-layer ms and a checksum of the
+gradients."""
 import json
 import os
 import sys
@@ -50,8 +50,7 @@ def main():
         res[name] = round(ms, 3)
         total += ms
         csum += float(dy.double().abs().sum())
-    print(json.dumps({"variant": os.environ.get("IC2_FLRB_VARIANT", "default"), "batch": batch,
-                      "total_ms": round(total, 3), "layers_ms": res, "checksum": csum}))
+    print(json.dumps({"batch": batch, "total_ms": round(total, 3), "layers_ms": res, "checksum": csum}))
 
 
 if __name__ == "__main__":
