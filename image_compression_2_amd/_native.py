@@ -14,7 +14,8 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libic2ops.so")
-# diagnostic builds (tools/build_abl.sh) are loaded instead only under IC2_DEV=1 with IC2_DEV_LIB set
+# a library built elsewhere (build_native.py: IC2_BUILD_DIR / IC2_LIB_OUT) is loaded instead only under IC2_DEV=1 with
+# IC2_DEV_LIB set
 if os.environ.get("IC2_DEV") == "1" and os.environ.get("IC2_DEV_LIB"):
     LIB_PATH = os.environ["IC2_DEV_LIB"]
 
@@ -78,7 +79,6 @@ _SIGS = {
     "ic2_conv_wino": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _F, _F, _F, _I, _P],
     "ic2_conv_wino_plan": [_I, _I, _I, _I, _I, _I],
     "ic2_conv_wino_preferred": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
-    "ic2_conv_wino_stamps": [_P, _I64],
     "ic2_synth_input_features": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _I, _P],
     "ic2_nchw_to_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "ic2_from_rgb_conv": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P],

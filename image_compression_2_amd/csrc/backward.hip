@@ -22,10 +22,9 @@ typedef short wg_s4 __attribute__((ext_vector_type(4)));
 // ------------------------------------------------------------------------------------------------
 // weight gradient as a GEMM over pixels: C[o][j] (j = one tap's 64 input channels) = sum_p A[o][p] B[p][j],
 // A = dy^T, B = the tap-shifted input.  Both operands are pixel-major in HBM (NHWC), so a 32-pixel chunk of
-// each is staged row-per-pixel in LDS and the MFMA fragments (8 consecutive pixels of one column) are read
-// with the transposing ds_read_b64_tr_b16 (two per fragment).  Tile 64 (o) x 64 (j) x 32 (p), 4 waves of
-// 32 x 32; the pixels are split over gridDim.y into f32 partial slabs summed in slice order by
-// wgrad_reduce_kernel (deterministic).  f32 operands: 16x16x4 f32 MFMAs on plain LDS reads.
+// each is staged row-per-pixel in LDS.  Tile 64 (o) x 64 (j) x 32 (p), 4 waves of 32 x 32; the pixels are split over
+// gridDim.y into f32 partial slabs summed in slice order by wgrad_reduce_kernel (deterministic).  This kernel: f32
+// operands, 16x16x4 f32 MFMAs on plain LDS reads; the 16-bit operands have their own (wgrad2_kernel below).
 constexpr int WG_BO = 64, WG_BJ = 64, WG_KP = 32;
 constexpr int WG_PITCH = WG_BO + 8;  // LDS row pitch (elements)
 
@@ -43,10 +42,9 @@ __device__ __forceinline__ wg_s4 wg_tr_read(const bf16_t* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wg_s4*)p);
 }
 
-template <typename T>
 __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs a) {
-  __shared__ __attribute__((aligned(16))) T sdy[WG_KP * WG_PITCH];
-  __shared__ __attribute__((aligned(16))) T sx[WG_KP * WG_PITCH];
+  __shared__ __attribute__((aligned(16))) float sdy[WG_KP * WG_PITCH];
+  __shared__ __attribute__((aligned(16))) float sx[WG_KP * WG_PITCH];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
@@ -59,8 +57,8 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs a) {
   const int c0 = (int)((int64_t)a.chunks * blockIdx.y / gridDim.y);
   const int c1 = (int)((int64_t)a.chunks * (blockIdx.y + 1) / gridDim.y);
   const int wo_ = wave >> 1, wj_ = wave & 1;           // this wave's 32 x 32 sub-tile
-  const T* dyg = reinterpret_cast<const T*>(a.dy);
-  const T* xg = reinterpret_cast<const T*>(a.x);
+  const float* dyg = reinterpret_cast<const float*>(a.dy);
+  const float* xg = reinterpret_cast<const float*>(a.x);
   // staging: thread -> (pixel row r = tid / 8, 8-element segment s = tid % 8) of each operand
   const int r = tid >> 3, seg = tid & 7;
   const int hwo = a.ho * a.wo;
@@ -73,7 +71,7 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs a) {
 
   // the next chunk's rows are loaded into registers while this chunk's MFMAs run (the loop was one exposed global
   // load round trip per 32 pixels)
-  constexpr int NV = sizeof(T) / 2;  // 16-B registers per 8-element row segment
+  constexpr int NV = 2;  // 16-B registers per 8-element row segment
   uint4 vd[NV], vx[NV];
   auto load_chunk = [&](int ch) {
     const int p = ch * WG_KP + r;
@@ -104,51 +102,18 @@ __global__ void __launch_bounds__(256) wgrad_kernel(WgradArgs a) {
     }
     __syncthreads();
     if (ch + 1 < c1) load_chunk(ch + 1);
-    if constexpr (sizeof(T) == 2) {
-      // A[m = o][k = p]: lane (g, li) = pixels 8g .. 8g+7 of column o; two transposed reads of 4 rows each.
-      // Within a 16-lane group, lane (tq = li / 4, tp = li % 4) reads row base + tq, elements 4 tp .. 4 tp + 3.
-      const int tq = li >> 2, tp = li & 3;
-      wg_bf16x8 af[2], bfr[2];
+    // 16x16x4 MFMA, lane (g, li) holds A[m = li][k = g] / B[k = g][n = li] per 4-pixel step (exact fp32)
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int col = wo_ * 32 + i * 16 + 4 * tp;
-        const wg_s4 lo = wg_tr_read(reinterpret_cast<const bf16_t*>(sdy) + (8 * g + tq) * WG_PITCH + col);
-        const wg_s4 hi = wg_tr_read(reinterpret_cast<const bf16_t*>(sdy) + (8 * g + 4 + tq) * WG_PITCH + col);
-        af[i] = __builtin_bit_cast(wg_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
+    for (int s = 0; s < WG_KP / 4; ++s) {
+      float av[2], bv[2];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = wj_ * 32 + j * 16 + 4 * tp;
-        const wg_s4 lo = wg_tr_read(reinterpret_cast<const bf16_t*>(sx) + (8 * g + tq) * WG_PITCH + col);
-        const wg_s4 hi = wg_tr_read(reinterpret_cast<const bf16_t*>(sx) + (8 * g + 4 + tq) * WG_PITCH + col);
-        bfr[j] = __builtin_bit_cast(wg_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
+      for (int i = 0; i < 2; ++i) av[i] = sdy[(4 * s + g) * WG_PITCH + wo_ * 32 + i * 16 + li];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bv[j] = sx[(4 * s + g) * WG_PITCH + wj_ * 32 + j * 16 + li];
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if constexpr (std::is_same<T, _Float16>::value)   // the f16 training path: f16 operands, same fragments
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wg_f16x8, af[i]),
-                                                               __builtin_bit_cast(wg_f16x8, bfr[j]), acc[i][j], 0, 0, 0);
-          else
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-        }
-    } else {
-      // f32: 16x16x4 MFMA, lane (g, li) holds A[m = li][k = g] / B[k = g][n = li] per 4-pixel step (exact fp32)
-      const float* fdy = reinterpret_cast<const float*>(sdy);
-      const float* fx = reinterpret_cast<const float*>(sx);
-#pragma unroll
-      for (int s = 0; s < WG_KP / 4; ++s) {
-        float av[2], bv[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) av[i] = fdy[(4 * s + g) * WG_PITCH + wo_ * 32 + i * 16 + li];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) bv[j] = fx[(4 * s + g) * WG_PITCH + wj_ * 32 + j * 16 + li];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-      }
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
     }
   }
   // C[o = o0 + 32 wo + 16 i + 4 g + rr][j = ci0 + 32 wj + 16 jj + li] -> part[split][o][tap][ci]
@@ -191,14 +156,17 @@ __global__ void __launch_bounds__(256) wgrad_reduce_oihw_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------
-// Weight gradient, 16-bit operands (round 4): the same GEMM over pixels with KP-pixel stages, double-buffered LDS
+// Weight gradient, 16-bit operands (round 4): the same GEMM over pixels with 64-pixel stages, double-buffered LDS
 // (one barrier per stage instead of two per 32 pixels) and the j axis flattened over (tap, input channel), so a
-// j tile of a 32-channel input covers several taps instead of reading a zero half.  Tile BT (o) x BT (j), 4 waves of
-// BT/2 x BT/2 (BT 64: 4 MFMAs 16x16x32 per 8 transposed fragment reads per k-step; BT 128: 16 per 16, for the
-// >= 128-channel layers); the next stage's rows are loaded into registers while the current one is computed.
-template <typename T, int KP, int BT>
+// j tile of a 32-channel input covers several taps instead of reading a zero half.  The MFMA fragments (8 consecutive
+// pixels of one column) are read with the transposing ds_read_b64_tr_b16 (two per fragment).  Tile 64 (o) x 64 (j),
+// 4 waves of 32 x 32 (4 MFMAs 16x16x32 per 8 transposed fragment reads per k-step; a 128-wide tile for the
+// >= 128-channel layers measured 2.4 % slower over the encoder's layers, profiles/r4p_wgrad_layers.txt); the next
+// stage's rows are loaded into registers while the current one is computed.
+template <typename T>
 __global__ void __launch_bounds__(256) wgrad2_kernel(WgradArgs a) {
   static_assert(sizeof(T) == 2, "16-bit operands");
+  constexpr int KP = 64, BT = 64;        // pixels per stage, tile edge
   constexpr int PITCH = BT + 8;          // LDS row pitch (elements)
   constexpr int STAGE = KP * PITCH;      // elements per operand and stage
   constexpr int SEGS = BT / 8;           // 16-B segments per staged row
@@ -325,15 +293,12 @@ static int wgrad_splits(const WgradArgs& a) {
   return (int)(sp < 1 ? 1 : sp);
 }
 
-// wgrad2_kernel's plan: bt x bt tiles, j over the flattened (tap, channel) axis, kp-pixel stages, `target`
-// workgroups with at least 4 stages each.  The 128-wide tile where both the output and the j extent fill it.
-// (128 only under knob IC2_WGRAD2=3: over the encoder's layers it measured 2.4 % slower than 64 everywhere,
-// profiles/r4p_wgrad_layers.txt)
-static int wgrad2_tile(int cout_p, int K) { return cout_p >= 128 && K >= 128 ? 128 : 64; }
-static int wgrad2_splits(const WgradArgs& a, int kp = 64, int target = 4096, int bt = 64) {
-  const int64_t tiles = ceil_div(a.cout_p, bt) * ceil_div((int64_t)a.kh * a.kw * a.cin_p, bt);
-  const int64_t chunks = ceil_div(a.P, kp);
-  int64_t sp = ceil_div(target, tiles);
+// wgrad2_kernel's plan: 64 x 64 tiles, j over the flattened (tap, channel) axis, 64-pixel stages, 4096 workgroups
+// (the split-K partials they write are re-read by wgrad_reduce_kernel) with at least 4 stages each
+static int wgrad2_splits(const WgradArgs& a) {
+  const int64_t tiles = ceil_div(a.cout_p, 64) * ceil_div((int64_t)a.kh * a.kw * a.cin_p, 64);
+  const int64_t chunks = ceil_div(a.P, 64);
+  int64_t sp = ceil_div(4096, tiles);
   if (sp > chunks / 4) sp = chunks / 4;
   if (sp > 256) sp = 256;
   return (int)(sp < 1 ? 1 : sp);
@@ -831,7 +796,7 @@ extern "C" int64_t ic2_conv_wgrad_ws_floats(int n, int h, int w, int cin_p, int 
   a.cin_p = cin_p; a.kh = kh; a.kw = kw;
   a.j_tiles = kh * kw * (int)ceil_div(cin_p, WG_BJ);
   // enough for either kernel (the 16-bit one plans its own splits)
-  const int sp = std::max(wgrad_splits(a), std::max(wgrad2_splits(a, 64, 4096, 64), wgrad2_splits(a, 64, 2048, 128)));
+  const int sp = std::max(wgrad_splits(a), wgrad2_splits(a));
   return (int64_t)sp * cout_p * kh * kw * cin_p;
 }
 
@@ -870,34 +835,20 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw, int dtype, 
   a.P = n * a.ho * a.wo;
   a.chunks = (int)ceil_div(a.P, WG_KP);
   a.j_tiles = kh * kw * (int)ceil_div(cin_p, WG_BJ);
-  // knob IC2_WGRAD2: 1 = the staged kernel, 64-wide tiles (default), 3 = 128-wide tiles where they fill, 0 = the
-  // round-3 kernel for 16-bit operands too
-  static const int v2 = knob("IC2_WGRAD2", 1);
-  const bool wide = v2 != 0 && dtype != IC2_F32;
-  const int bt = v2 == 3 ? wgrad2_tile(cout_p, kh * kw * cin_p) : 64;
-  // knob IC2_WGRAD_TARGET: workgroups per launch the K split aims at (64-wide tiles; the split-K partials it writes
-  // are re-read by wgrad_reduce_kernel)
-  static const int target = std::max(64, std::min(knob("IC2_WGRAD_TARGET", 4096), 4096));  // <= the workspace plan's
-  const int splits = wide ? wgrad2_splits(a, 64, bt == 128 ? target / 2 : target, bt) : wgrad_splits(a);
+  const bool wide = dtype != IC2_F32;  // 16-bit operands: the staged kernel
+  const int splits = wide ? wgrad2_splits(a) : wgrad_splits(a);
   const int64_t total = (int64_t)cout_p * kh * kw * cin_p;
   IC2_CHECK_ARG(ws_floats >= splits * total, "conv_wgrad: workspace too small (%lld < %lld floats)",
                 (long long)ws_floats, (long long)(splits * total));
   hipStream_t s = as_stream(stream);
   if (wide) {
     a.chunks = (int)ceil_div(a.P, 64);
-    const dim3 grid((unsigned)(ceil_div(cout_p, bt) * ceil_div((int64_t)kh * kw * cin_p, bt)), (unsigned)splits);
-    if (bt == 128) {
-      if (dtype == IC2_BF16) hipLaunchKernelGGL((wgrad2_kernel<bf16_t, 64, 128>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((wgrad2_kernel<_Float16, 64, 128>), grid, dim3(256), 0, s, a);
-    } else {
-      if (dtype == IC2_BF16) hipLaunchKernelGGL((wgrad2_kernel<bf16_t, 64, 64>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((wgrad2_kernel<_Float16, 64, 64>), grid, dim3(256), 0, s, a);
-    }
+    const dim3 grid((unsigned)(ceil_div(cout_p, 64) * ceil_div((int64_t)kh * kw * cin_p, 64)), (unsigned)splits);
+    if (dtype == IC2_BF16) hipLaunchKernelGGL(wgrad2_kernel<bf16_t>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(wgrad2_kernel<_Float16>, grid, dim3(256), 0, s, a);
   } else {
     const dim3 grid((unsigned)(ceil_div(cout_p, WG_BO) * a.j_tiles), (unsigned)splits);
-    if (dtype == IC2_BF16) hipLaunchKernelGGL(wgrad_kernel<bf16_t>, grid, dim3(256), 0, s, a);
-    else if (dtype == IC2_F16) hipLaunchKernelGGL(wgrad_kernel<_Float16>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, s, a);
   }
   if (oihw_cout > 0)
     hipLaunchKernelGGL(wgrad_reduce_oihw_kernel, dim3(grid_for(total)), dim3(256), 0, s, workspace, dw, total, splits,

@@ -35,8 +35,8 @@ struct IgemmArgs {
   int nq;       // K-chunks: K / 32 (K / 64 for the 8-phase kernels)
   int tiles_o;  // ceil(cout_p / BO)
   int nblocks;  // tiles_o * tiles_p
-  int group;    // p-tiles per o-sweep (tile_coords)
-  int korder;   // 8-phase kernels: 0 = tap-major K, 1 = channel-major K (taps innermost)
+  int group;    // implicit GEMMs: p-tiles per o-sweep (tile_coords); every launch sets 1
+  int korder;   // 8-phase kernels: 1 = channel-major K (taps innermost), what every launch sets; 0 = tap-major K
   int o_base;   // 8-phase kernels: first output channel of this launch (a cout_p split over two tile shapes)
   int tile_base;  // 8-phase kernels: first logical tile of this launch (the split tail of a grid, see ig_plan)
   int act;
@@ -209,9 +209,10 @@ __device__ __forceinline__ void ig_epilogue(const IgemmArgs& a, const f32x4 (&ac
   }
 }
 
-// logical tile -> (o_tile, p_tile), bijective: runs of `group` consecutive p-tiles sweep one o-tile at a
-// time, so the blocks resident on one XCD at once share a single weight panel in its L2 (all o-tiles of
-// a p-tile side by side would keep tiles_o panels live).  The last run may be shorter.
+// logical tile -> (o_tile, p_tile), bijective: runs of `group` consecutive p-tiles sweep one o-tile at a time.  The
+// host sets group = 1 -- p-tile-major, the o-tiles of a p-tile side by side, measured best -- and the tail split of the
+// 8-phase grid (ig_plan) relies on that order.  The general map stays because the 8-phase kernels measured ~1 % slower
+// with the two-line group-1 map in its place (profiles/r11_conv_prune.txt).
 __device__ __forceinline__ void tile_coords(int logical, int tiles_o, int tiles_p, int group, int& o_tile,
                                             int& p_tile) {
   const int per = group * tiles_o;

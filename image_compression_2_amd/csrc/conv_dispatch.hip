@@ -10,28 +10,15 @@
 
 namespace ic2 {
 
-// p-tiles per o-sweep of the implicit GEMMs' tile order (tile_coords); knob IC2_IGEMM_GROUP
-static int igemm_group() {
-  static const int group = [] {
-    const int g = knob("IC2_IGEMM_GROUP", 1);  // 1 = o-tiles of a p-tile side by side (measured best)
-    return g >= 1 ? g : 1;
-  }();
-  return group;
-}
-
 // hg4 instance: o-tile 96 when cout_p % 192 == 0 (two 96-wide o-tiles on 8 x 32-pixel tiles: a weight slab feeds 256
 // pixels instead of the 192-wide tile's 128, so 2.1 instead of 3.4 LDS-DMA pieces per 24 MFMAs; SG3-T-256 L11
-// 2.27 -> 2.15 ms, profiles/r4x_hg4_o96.txt), 128 when cout_p % 128 == 0, else 64; IC2_HG4_BO = 192 / 128 / 96 / 64
-// forces one where it divides.  Pixel tile 32 or 16 wide, whichever pads the output less (a 96-wide o-tile whose
-// output pads less on 16-wide tiles runs as the 192-wide 16-wide-tile instance).
+// 2.27 -> 2.15 ms, profiles/r4x_hg4_o96.txt), 128 when cout_p % 128 == 0, else 64.  Pixel tile 32 or 16 wide,
+// whichever pads the output less (a 96-wide o-tile whose output pads less on 16-wide tiles runs as the 192-wide
+// 16-wide-tile instance).
 static H4Plan h4_plan(int n, int ho, int wo, int cout_p) {
-  static const int force_bo = knob("IC2_HG4_BO", 0);
   H4Plan p;
   p.bo = cout_p % 192 == 0 ? 96 : cout_p % 128 == 0 ? 128 : 64;
-  if ((force_bo == 192 || force_bo == 128 || force_bo == 96 || force_bo == 64) && cout_p % force_bo == 0)
-    p.bo = force_bo;
-  const int bp32 = p.bo <= 128 ? 256 : 128, bp16 = p.bo <= 128 && p.bo != 96 ? 256 : 128;
-  const int th32 = bp32 / 32, th16 = bp16 / 16;
+  const int th32 = 8, th16 = p.bo != 96 ? 16 : 8;  // 256-pixel tiles; 128 pixels under the 192-wide o-tile
   const int64_t a32 = ceil_div(ho, th32) * th32 * ceil_div(wo, 32) * 32;
   const int64_t a16 = ceil_div(ho, th16) * th16 * ceil_div(wo, 16) * 16;
   p.tw32 = a32 <= a16;
@@ -54,20 +41,16 @@ static bool hg4_by_default(const H4Plan& p, int cin_p, int cout_p, int ho, int w
   if (p.blocks < 512) return false;
   const double util = (double)ho * wo / (double)p.area;
   // inputs up to 512 channels (the split encoder's 384-wide block-1 conv2: og1 -> hg4 + fused statistics, C4
-  // +1.1 %, profiles/r3_hg4_maxc_ab.txt); knob IC2_HG4_MAXC for the A/B
-  static const int maxc = knob("IC2_HG4_MAXC", 512);
-  return cin_p <= maxc && cout_p <= 192 && util >= 0.93;
+  // +1.1 %, profiles/r3_hg4_maxc_ab.txt)
+  return cin_p <= 512 && cout_p <= 192 && util >= 0.93;
 }
 
 // ------------------------------------------------------------------------------------------------
 // implicit-GEMM tile instance (kIgTiles, conv_plan.h) and K split.
-// Knobs (IC2_DEV=1 only): IC2_IGEMM_TILE=1..7 forces a bf16 tile (the tests exercise every instance on small
-// problems), IC2_IGEMM_G8N=0 keeps the cout_p <= 128 layers off the 8-phase kernel, IC2_IGEMM_SPLITK=0 disables
-// split-K.
+// Knob (IC2_DEV=1 only): IC2_IGEMM_TILE=1..7 forces a bf16 tile (the tests exercise every instance on small
+// problems).
 static void ig_plan(ConvPlan& c, int dtype, int64_t M, int cout_p, int cin_p, int kh, int kw, int64_t x_elems, bool x8) {
   static const int forced = knob("IC2_IGEMM_TILE", 0);
-  static const bool g8n = knob("IC2_IGEMM_G8N", 1) != 0;
-  static const bool splitk = knob("IC2_IGEMM_SPLITK", 1) != 0;
   const int64_t K = (int64_t)kh * kw * cin_p;
   int tile = IG_F32_128x128;
   c.splits = 1;
@@ -91,18 +74,15 @@ static void ig_plan(ConvPlan& c, int dtype, int64_t M, int cout_p, int cin_p, in
     const bool odd128 = cout_p % 256 == 128 && cout_p > 128;
     // small grids (the encoder's 512-wide blocks at <= 32^2): the same 8-phase tiles with K split over
     // gridDim.y so the launch reaches ~1 workgroup per CU, instead of the 4-stage 128 x 128 split-K tile
-    static const bool g8_splitk = knob("IC2_G8_SPLITK", 1) != 0;
     const int64_t g6 = ceil_div(M, 256) * ((cout_p + 255) / 256), g7 = ceil_div(M, 512) * ((cout_p + 127) / 128);
     const bool k_deep = K / 64 >= 32;
     int g8_split = 1;
-    // knob IC2_G8_TARGET: workgroups the split aims at (default 240, ~1 per CU of the 1-workgroup-per-CU kernel)
-    static const int g8_target = knob("IC2_G8_TARGET", 240);
     // (a full-K grid of 1-2 rounds is not split for wave balance: SG3-T-256 L0-L3's 362 workgroups as 724 half-K ones
     // measured 10 % slower, the f32 partials and the combine costing more than the idle tail, r6_schedule_ab.txt)
     if (fits8 && cout_p > 128 && !odd128 && g6 >= 240) tile = IG_G8_OG2;
-    else if (g8n && fits8 && (odd128 || (cout_p > 64 && cout_p <= 128)) && g7 >= 240) tile = IG_G8_OG1;
-    else if (g8_splitk && splitk && fits8 && k_deep && cout_p > 128 && !odd128)
-      tile = IG_G8_OG2, g8_split = (int)ceil_div(g8_target, g6);
+    else if (fits8 && (odd128 || (cout_p > 64 && cout_p <= 128)) && g7 >= 240) tile = IG_G8_OG1;
+    else if (fits8 && k_deep && cout_p > 128 && !odd128)
+      tile = IG_G8_OG2, g8_split = (int)ceil_div(240, g6);  // aims at ~1 workgroup per CU
     if (g8_split > 1) {
       int64_t sp = g8_split;
       if (sp > K / 64 / 8) sp = K / 64 / 8;  // >= 8 K-tiles of 64 per slice
@@ -119,13 +99,12 @@ static void ig_plan(ConvPlan& c, int dtype, int64_t M, int cout_p, int cin_p, in
   // 2r half-K workgroups -- one round of half the time -- behind a launch of the whole rounds; the tail's f32 partials
   // are combined over its pixels only (SG3-T-256 L0-L2 at batch 32: 362 tiles = 256 + 106, 2 rounds -> 1.5).  Round 6
   // split every tile of such a grid instead (724 half-K workgroups: 10 % slower, every tile paying the partials).
-  // The tail's pixels are those of its p-tiles only in the p-tile-major tile order (group 1).
-  static const bool g8_tail = knob("IC2_G8_TAIL", 1) != 0;
-  if (tile == IG_G8_OG2 && g8_tail && splitk && igemm_group() == 1 && K / 64 >= 16 && M * cout_p < (1LL << 31)) {
+  // The tail's pixels are those of its p-tiles in the p-tile-major tile order (tile_coords, group 1).
+  if (tile == IG_G8_OG2 && K / 64 >= 16 && M * cout_p < (1LL << 31)) {
     const int64_t tiles_o = (cout_p + 255) / 256, tiles = ceil_div(M, 256) * tiles_o, rem = tiles % 256;
     if (tiles > 256 && rem > 0 && rem <= 128 && (tiles - rem) % tiles_o == 0) c.tail = true;
   }
-  if (tile < IG_G8_OG2 && splitk) {
+  if (tile < IG_G8_OG2) {
     // fewer workgroups than ~1.25 per CU: split K so the launch reaches ~512 workgroups, each slice
     // keeping >= 8 chunks of 32
     const int64_t blocks = ceil_div(M, kIgTiles[tile].bp) * ceil_div(cout_p, kIgTiles[tile].bo);
@@ -139,11 +118,9 @@ static void ig_plan(ConvPlan& c, int dtype, int64_t M, int cout_p, int cin_p, in
   }
 }
 
-// the halo kernel for bf16 3x3 convs with cin_p in {32, 64, 96}, cout_p in {32, 64} and >= 64K output
-// pixels; knob IC2_HCONV=0 keeps them on the implicit GEMM
+// the halo kernel for bf16 3x3 convs with cin_p in {32, 64, 96}, cout_p in {32, 64} and >= 64K output pixels
 static bool hconv_eligible(int dtype, int64_t M, int cin_p, int cout_p, int kh, int kw) {
-  static const bool on = knob("IC2_HCONV", 1) != 0;
-  return on && is16(dtype) && kh == 3 && kw == 3 && (cin_p == 32 || cin_p == 64 || cin_p == 96) &&
+  return is16(dtype) && kh == 3 && kw == 3 && (cin_p == 32 || cin_p == 64 || cin_p == 96) &&
          (cout_p == 32 || cout_p == 64) && M >= 65536;
 }
 // its TH x 32-pixel tiles per image
@@ -152,8 +129,7 @@ static int64_t hconv_tiles(int cin_p, int ho, int wo) { return ceil_div(wo, 32) 
 // (the ToRGB kernel maps output pixel p to input pixel p: 1x1, no padding)
 static bool torgb_eligible(int dtype, int cin_p, int cout_valid, int kh, int kw, int pad, int out_layout,
                            int out_dtype) {
-  static const bool on = knob("IC2_TORGB", 1) != 0;
-  return on && is16(dtype) && kh == 1 && kw == 1 && pad == 0 && cout_valid <= 4 && out_layout == IC2_LAYOUT_NCHW &&
+  return is16(dtype) && kh == 1 && kw == 1 && pad == 0 && cout_valid <= 4 && out_layout == IC2_LAYOUT_NCHW &&
          out_dtype == IC2_F32 && (cin_p == 32 || cin_p == 64 || cin_p == 128);
 }
 
@@ -179,14 +155,14 @@ static ConvPlan conv_choice(int dtype, int out_layout, int out_dtype, int n, int
   const bool x8 = dtype != IC2_F16X2 || (cin_p / 2) % 64 == 0;
   if (x3) dtype = dtype == IC2_F16X2 ? IC2_F16 : IC2_BF16;
   // hg4 ahead of the halo direct conv for >= 96 input channels (SG3-T-1024 L11: 1532 -> 1363 us at batch 8); the
-  // 32 / 64-channel encoder layers stay on hconv (faster there).  Knob IC2_HG4_HCONV = 0 / 1: never / always.
-  static const int hg4_mode = knob("IC2_HG4", 1), hg4_over_hconv = knob("IC2_HG4_HCONV", -1);
+  // 32 / 64-channel encoder layers stay on hconv (faster there)
+  static const int hg4_mode = knob("IC2_HG4", 1);
   bool hg4_ok = hg4_mode && hg4_legal(dtype, cin_p, cout_p, kh, kw, x_elems);
   if (hg4_ok) {
     c.h4 = h4_plan(n, ho, wo, cout_p);
     hg4_ok = hg4_mode == 2 || hg4_by_default(c.h4, cin_p, cout_p, ho, wo);
   }
-  const bool hg4_pref = hg4_over_hconv == 1 || (hg4_over_hconv < 0 && cin_p >= 96);
+  const bool hg4_pref = cin_p >= 96;
   if (!x3 && torgb_eligible(dtype, cin_p, cout_valid, kh, kw, pad, out_layout, out_dtype)) c.kind = CK_TORGB;
   else if (hg4_ok && hg4_pref) c.kind = CK_HG4;
   else if (!x3 && hconv_eligible(dtype, M, cin_p, cout_p, kh, kw)) c.kind = CK_HCONV;
@@ -198,10 +174,8 @@ static ConvPlan conv_choice(int dtype, int out_layout, int out_dtype, int n, int
   if (c.kind != CK_IGEMM) return c;
   ig_plan(c, dtype, M, cout_p, cin_p, kh, kw, x_elems, x8);
   // an odd multiple of 128 above 128 (384: SG3-T-256 L9, SG3-T-1024 L7): the 256-wide tile on all but the last
-  // 128 channels, the 128 x 512 tile on those (both read the same input panel); knob IC2_IGEMM_SPLIT=0 keeps one
-  // 128 x 512 launch
-  static const bool split = knob("IC2_IGEMM_SPLIT", 1) != 0;
-  c.split384 = is16(dtype) && c.tile == IG_G8_OG1 && split && cout_p % 256 == 128 && cout_p > 128 &&
+  // 128 channels, the 128 x 512 tile on those (both read the same input panel)
+  c.split384 = is16(dtype) && c.tile == IG_G8_OG1 && cout_p % 256 == 128 && cout_p > 128 &&
                ceil_div(M, 256) >= 240;
   if (c.tail) {  // the tail: the tiles past the whole rounds; its pixels: that tile's p-tile (p-tile-major order) on
     const int64_t tiles_o = (cout_p + 255) / 256, g6 = ceil_div(M, 256) * tiles_o;
@@ -239,8 +213,11 @@ static bool conv_kind_reads_blocked(ConvKind kind, int dtype) {
 // Images per launch: the buffer-descriptor kernels (8-phase, hg4) address < 2^31 bytes per operand, so a batch whose
 // input exceeds that runs in chunks of whole images (each chunk with its own launch plan) instead of falling back to
 // the generic tile (SG3-T-1024 / the 1024^2 encoder at batch 8: 1024^2 x 192 x 2 B = 403 MB per image).
-static int conv_chunk_n(int dtype, int n, int h, int w_, int cin_p) {
-  const int64_t per_img = (int64_t)h * w_ * x_pix_of(dtype, cin_p) * (dtype == IC2_F32 ? 4 : 2);
+int64_t conv_x_img_bytes(int dtype, int h, int w_, int cin_p) {
+  return (int64_t)h * w_ * x_pix_of(dtype, cin_p) * (dtype == IC2_F32 ? 4 : 2);
+}
+int conv_chunk_n(int dtype, int n, int h, int w_, int cin_p) {
+  const int64_t per_img = conv_x_img_bytes(dtype, h, w_, cin_p);
   if ((int64_t)n * per_img < (int64_t)kOob || per_img >= (int64_t)kOob) return n;
   const int64_t c = ((int64_t)kOob - 1) / per_img;
   const int64_t chunks = ceil_div(n, c);
@@ -255,9 +232,8 @@ static ConvPlan conv_choice_chunked(int dtype, int out_layout, int out_dtype, in
 
 // The launch arguments of a plain conv: bias only, no activation, NHWC input and output, no fused GroupNorm.  The
 // callers set what differs.
-static IgemmArgs make_igemm_args(const void* x, const void* w, void* y, const float* bias, int dtype, int out_dtype,
-                                 int n, int h, int w_, int cin_p, int cout_p, int cout_valid, int kh, int kw, int pad,
-                                 float out_mul) {
+IgemmArgs make_igemm_args(const void* x, const void* w, void* y, const float* bias, int dtype, int out_dtype, int n,
+                          int h, int w_, int cin_p, int cout_p, int cout_valid, int kh, int kw, int pad, float out_mul) {
   IgemmArgs a{};
   a.x = x; a.w = w; a.y = y; a.bias = bias;
   a.n = n; a.h = h; a.w_ = w_; a.cin_p = cin_p; a.cout_p = cout_p; a.cout_valid = cout_valid;
@@ -265,11 +241,37 @@ static IgemmArgs make_igemm_args(const void* x, const void* w, void* y, const fl
   a.M = (int)((int64_t)n * a.ho * a.wo); a.K = kh * kw * cin_p; a.nq = a.K / 32;
   a.act_gain = 1.f; a.clamp = -1.f; a.out_mul = out_mul;
   a.out_layout = IC2_LAYOUT_NHWC; a.out_dtype = out_dtype;
-  a.group = 1;
+  a.group = 1;   // p-tile-major tile order (tile_coords)
+  a.korder = 1;  // channel-major K (igemm8.hip)
   a.x_pix = x_pix_of(dtype, cin_p);
   a.x_hb32 = x_hb32_of(dtype, cin_p);
   ig_set_input_layout(a, false);
   return a;
+}
+
+int conv_check_call(const char* who, ConvCall& c) {
+  // the input layout rides in the bits above the activation (ic2ops.h IC2_ACT_IN_LAYOUT)
+  const int in_layout = IC2_ACT_IN_LAYOUT_OF(c.act);
+  c.act = IC2_ACT_OF(c.act);
+  IC2_CHECK_ARG(in_layout == IC2_LAYOUT_NHWC || in_layout == IC2_LAYOUT_NHWC16, "%s: bad input layout %d", who,
+                in_layout);
+  c.in_blocked = in_layout == IC2_LAYOUT_NHWC16;
+  IC2_CHECK_ARG(c.out_dtype == IC2_F32 || c.out_dtype == IC2_BF16 ||
+                    ((c.out_dtype == IC2_F16 || c.out_dtype == IC2_F16_IEEE) && c.out_layout != IC2_LAYOUT_NCHW),
+                "%s: bad out dtype %d", who, c.out_dtype);
+  IC2_CHECK_ARG(c.cin_p > 0 && c.cin_p % 32 == 0 && c.cout_p > 0 && c.cout_p % 32 == 0,
+                "%s: channel strides must be positive multiples of 32 (cin_p=%d cout_p=%d)", who, c.cin_p, c.cout_p);
+  IC2_CHECK_ARG(c.n > 0 && c.h > 0 && c.w_ > 0 && c.kh > 0 && c.kw > 0 && c.pad >= 0, "%s: bad geometry", who);
+  IC2_CHECK_ARG(c.ho == c.h + 2 * c.pad - c.kh + 1 && c.wo == c.w_ + 2 * c.pad - c.kw + 1 && c.ho > 0 && c.wo > 0,
+                "%s: output size %dx%d does not match input %dx%d, k=%dx%d, pad=%d", who, c.ho, c.wo, c.h, c.w_, c.kh,
+                c.kw, c.pad);
+  IC2_CHECK_ARG(c.out_layout == IC2_LAYOUT_NHWC || c.out_layout == IC2_LAYOUT_NHWC16 ||
+                    (c.out_layout == IC2_LAYOUT_NCHW && c.out_dtype == IC2_F32 && c.cout_valid > 0 &&
+                     c.cout_valid <= c.cout_p),
+                "%s: NCHW output needs f32 and 0 < cout_valid <= cout_p (layout %d)", who, c.out_layout);
+  c.out_ieee = c.out_dtype == IC2_F16_IEEE;
+  if (c.out_ieee) c.out_dtype = IC2_F16;
+  return IC2_OK;
 }
 
 }  // namespace ic2
@@ -290,19 +292,16 @@ extern "C" const char* ic2_conv_plan(int dtype, int out_dtype, int out_layout, i
 }
 
 // The filtered lrelu -> conv hand-off stays channel-blocked where the consumer reads it that way and does not lose
-// more than the filtered lrelu gains (per kernel family, profiles/r7_act_blocked_ab.txt); knobs IC2_ACT_BLOCKED_WINO /
-// _HG4 / _TORGB = 0 / 1 (IC2_DEV=1) override the family defaults below
+// more than the filtered lrelu gains (per kernel family, profiles/r7_act_blocked_ab.txt): Winograd and hg4 do, ToRGB
+// does not (+20 us against its filtered lrelu's -19 us; launching it on blocked input stays legal)
 extern "C" int ic2_conv_accepts_nhwc16(int dtype, int out_dtype, int out_layout, int n, int h, int w_, int cin_p,
                                        int cout_p, int cout_valid, int kh, int kw, int pad) {
-  static const bool on_wino = knob("IC2_ACT_BLOCKED_WINO", 1) != 0, on_hg4 = knob("IC2_ACT_BLOCKED_HG4", 1) != 0,
-                    on_torgb = knob("IC2_ACT_BLOCKED_TORGB", 0) != 0;  // ToRGB +20 us vs its filtered lrelu's -19 us
   const int ho = h + 2 * pad - kh + 1, wo = w_ + 2 * pad - kw + 1;
   if (n <= 0 || ho <= 0 || wo <= 0 || cin_p <= 0 || cin_p % 32 || cout_p <= 0 || cout_p % 32) return 0;
-  if (ic2_conv_wino_preferred(dtype, n, h, w_, cin_p, cout_p, kh, kw, pad)) return on_wino;
+  if (ic2_conv_wino_preferred(dtype, n, h, w_, cin_p, cout_p, kh, kw, pad)) return 1;
   int nc;
   const ConvPlan c = conv_choice_chunked(dtype, out_layout, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, &nc);
-  if (!conv_kind_reads_blocked(c.kind, dtype)) return 0;
-  return c.kind == CK_HG4 ? on_hg4 : on_torgb;
+  return c.kind == CK_HG4 && conv_kind_reads_blocked(c.kind, dtype);
 }
 
 extern "C" int64_t ic2_conv_igemm_ws_bytes(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw,
@@ -319,80 +318,42 @@ extern "C" int ic2_conv_igemm_ws(const void* x, const void* w, void* y, int dtyp
                                  float clamp, float out_mul, int out_layout, void* workspace, int64_t ws_bytes,
                                  void* stream) {
   IC2_CHECK_ARG(x && w && y, "conv_igemm: null pointer");
-  // the input layout rides in the bits above the activation (ic2ops.h IC2_ACT_IN_LAYOUT)
-  const int act_flags = act, in_layout = IC2_ACT_IN_LAYOUT_OF(act_flags);
-  act = IC2_ACT_OF(act_flags);
-  IC2_CHECK_ARG(in_layout == IC2_LAYOUT_NHWC || in_layout == IC2_LAYOUT_NHWC16, "conv_igemm: bad input layout %d",
-                in_layout);
-  const bool in_blocked = in_layout == IC2_LAYOUT_NHWC16;
   IC2_CHECK_ARG(dtype == IC2_F32 || dtype == IC2_BF16 || dtype == IC2_F16 || dtype == IC2_BF16X3 || dtype == IC2_F16X2,
                 "conv_igemm: bad dtype %d", dtype);
   IC2_CHECK_ARG(dtype != IC2_BF16X3 || (cin_p % 96 == 0 && out_layout == IC2_LAYOUT_NHWC),
                 "conv_igemm: split-bf16 input needs cin_p = 3 x a multiple of 32 and NHWC output (cin_p=%d)", cin_p);
   IC2_CHECK_ARG(dtype != IC2_F16X2 || (cin_p % 64 == 0 && out_layout == IC2_LAYOUT_NHWC),
                 "conv_igemm: split-weight f16 input needs cin_p = 2 x a multiple of 32 and NHWC output (cin_p=%d)", cin_p);
-  IC2_CHECK_ARG(out_dtype == IC2_F32 || out_dtype == IC2_BF16 ||
-                    ((out_dtype == IC2_F16 || out_dtype == IC2_F16_IEEE) && out_layout != IC2_LAYOUT_NCHW),
-                "conv_igemm: bad out dtype %d", out_dtype);
-  IC2_CHECK_ARG(cin_p > 0 && cin_p % 32 == 0 && cout_p > 0 && cout_p % 32 == 0,
-                "conv_igemm: channel strides must be positive multiples of 32 (cin_p=%d cout_p=%d)", cin_p, cout_p);
-  IC2_CHECK_ARG(n > 0 && h > 0 && w_ > 0 && kh > 0 && kw > 0 && pad >= 0, "conv_igemm: bad geometry");
-  IC2_CHECK_ARG(ho == h + 2 * pad - kh + 1 && wo == w_ + 2 * pad - kw + 1,
-                "conv_igemm: output size %dx%d does not match input %dx%d, k=%dx%d, pad=%d", ho, wo, h, w_, kh, kw, pad);
-  IC2_CHECK_ARG(out_layout == IC2_LAYOUT_NHWC || out_layout == IC2_LAYOUT_NHWC16 ||
-                    (out_layout == IC2_LAYOUT_NCHW && out_dtype == IC2_F32 && cout_valid > 0 && cout_valid <= cout_p),
-                "conv_igemm: NCHW output needs f32 and 0 < cout_valid <= cout_p (layout %d)", out_layout);
+  ConvCall cc{x, w, y, oscale, bias, dtype, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, ho, wo,
+              act, slope, act_gain, clamp, out_mul, out_layout};
+  if (const int rc = conv_check_call("conv_igemm", cc)) return rc;
   IC2_CHECK_ARG(((uintptr_t)oscale | (uintptr_t)bias | (uintptr_t)workspace) % 16 == 0,
                 "conv_igemm: oscale/bias/workspace must be 16-byte aligned");
-  const int nc = conv_chunk_n(dtype, n, h, w_, cin_p);
-  if (nc < n) {
-    const int64_t x_img = (int64_t)h * w_ * x_pix_of(dtype, cin_p) * (dtype == IC2_F32 ? 4 : 2);
-    const int64_t y_img = out_layout == IC2_LAYOUT_NCHW ? (int64_t)cout_valid * ho * wo * 4
-                                                        : (int64_t)ho * wo * cout_p * (out_dtype == IC2_F32 ? 4 : 2);
-    for (int n0 = 0; n0 < n; n0 += nc) {
-      const int nn = n - n0 < nc ? n - n0 : nc;
-      const int rc = ic2_conv_igemm_ws(reinterpret_cast<const char*>(x) + n0 * x_img, w,
-                                       reinterpret_cast<char*>(y) + n0 * y_img, dtype, out_dtype, nn, h, w_, cin_p,
-                                       cout_p, cout_valid, kh, kw, pad, ho, wo,
-                                       oscale ? oscale + (int64_t)n0 * cout_p : nullptr, bias, act_flags, slope,
-                                       act_gain, clamp, out_mul, out_layout, workspace, ws_bytes, stream);
-      if (rc != IC2_OK) return rc;
-    }
-    return IC2_OK;
-  }
-  IC2_CHECK_ARG((int64_t)n * ho * wo < (1LL << 30), "conv_igemm: too many output pixels");
-  const int out_ieee = out_dtype == IC2_F16_IEEE;
-  if (out_ieee) out_dtype = IC2_F16;
-  IgemmArgs a = make_igemm_args(x, w, y, bias, dtype, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, out_mul);
-  a.oscale = oscale; a.ws = reinterpret_cast<float*>(workspace);
-  a.act = act; a.slope = slope; a.act_gain = act_gain; a.clamp = clamp;
-  a.out_layout = out_layout; a.out_ieee = out_ieee;
-  ig_set_input_layout(a, in_blocked);
-  a.group = igemm_group();
-  // channel-major K order: s148 +3 %, s148b +5 %, s148c +7 %, C2 +2.6 % (profiles/r2f_korder.txt)
-  static const int korder = knob("IC2_IGEMM_KORDER", 1);
-  a.korder = korder;
   hipStream_t s = as_stream(stream);
-  ConvPlan c = conv_choice(dtype, out_layout, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad);
-  IC2_CHECK_ARG(!in_blocked || conv_kind_reads_blocked(c.kind, dtype),
-                "conv_igemm: channel-blocked (NHWC16) input is read by the hg4 halo kernels and ToRGB only, with plain "
-                "bf16 / f16 operands; this geometry runs as %s (ic2_conv_accepts_nhwc16 says which do)",
-                conv_choice_name(c));
-  // the one downgrade of a plan: a split form without its workspace (a plan query cannot know the caller's buffer)
-  if (c.ws_bytes > 0 && (workspace == nullptr || ws_bytes < c.ws_bytes)) c.splits = 1, c.tail = false, c.ws_bytes = 0;
-  const bool f16 = dtype == IC2_F16 || dtype == IC2_F16X2;  // the kernels' operand type
-  switch (c.kind) {
-    case CK_TORGB: launch_torgb(a, f16, s); break;
-    case CK_HG4: launch_hg4(a, c.h4, f16, false, s); break;
-    case CK_HCONV: launch_hconv(a, false, f16, s); break;
-    case CK_IGEMM:
-      if (c.tile >= IG_G8_OG2) launch_igemm8(a, c, f16, s);
-      else launch_igemm(a, c.tile, f16, c.splits, s);
-      if (c.ws_bytes > 0) launch_splitk_reduce(a, c.tail ? 2 : c.splits, c.p_lo, s);
-      break;
-  }
-  IC2_CHECK_LAUNCH("conv_igemm");
-  return IC2_OK;
+  return conv_for_chunks(cc, [&](IgemmArgs& a) -> int {
+    IC2_CHECK_ARG((int64_t)a.n * ho * wo < (1LL << 30), "conv_igemm: too many output pixels");
+    a.ws = reinterpret_cast<float*>(workspace);
+    ConvPlan c = conv_choice(dtype, out_layout, cc.out_dtype, a.n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad);
+    IC2_CHECK_ARG(!cc.in_blocked || conv_kind_reads_blocked(c.kind, dtype),
+                  "conv_igemm: channel-blocked (NHWC16) input is read by the hg4 halo kernels and ToRGB only, with "
+                  "plain bf16 / f16 operands; this geometry runs as %s (ic2_conv_accepts_nhwc16 says which do)",
+                  conv_choice_name(c));
+    // the one downgrade of a plan: a split form without its workspace (a plan query cannot know the caller's buffer)
+    if (c.ws_bytes > 0 && (workspace == nullptr || ws_bytes < c.ws_bytes)) c.splits = 1, c.tail = false, c.ws_bytes = 0;
+    const bool f16 = dtype == IC2_F16 || dtype == IC2_F16X2;  // the kernels' operand type
+    switch (c.kind) {
+      case CK_TORGB: launch_torgb(a, f16, s); break;
+      case CK_HG4: launch_hg4(a, c.h4, f16, false, s); break;
+      case CK_HCONV: launch_hconv(a, false, f16, s); break;
+      case CK_IGEMM:
+        if (c.tile >= IG_G8_OG2) launch_igemm8(a, c, f16, s);
+        else launch_igemm(a, c.tile, f16, c.splits, s);
+        if (c.ws_bytes > 0) launch_splitk_reduce(a, c.tail ? 2 : c.splits, c.p_lo, s);
+        break;
+    }
+    IC2_CHECK_LAUNCH("conv_igemm");
+    return IC2_OK;
+  });
 }
 
 extern "C" int ic2_conv_igemm(const void* x, const void* w, void* y, int dtype, int out_dtype, int n, int h, int w_,
@@ -412,11 +373,8 @@ bool conv_gn_in_supported(int dtype, int n, int h, int w_, int cin_p, int cout_p
   return hconv_eligible(dtype, (int64_t)n * ho * wo, cin_p, cout_p, kh, kw);
 }
 
-// rows of the statistics-epilogue kernel's pixel tile: 12 for the 64-wide outputs (knob IC2_X3_GN_T12=0: 8), else 8
-static int x3_gn_th(int cout_p) {
-  static const bool t12 = knob("IC2_X3_GN_T12", 1) != 0;
-  return cout_p == 64 && t12 ? 12 : 8;
-}
+// rows of the statistics-epilogue kernel's pixel tile: 12 for the 64-wide outputs, else 8
+static int x3_gn_th(int cout_p) { return cout_p == 64 ? 12 : 8; }
 // split-bf16 (IC2_BF16X3) / split-weight f16 (IC2_F16X2) conv with f32 output: the hg4 instance the plan picks (per
 // chunk of *nc images, as ic2_conv_igemm_ws launches it) carries the statistics in its epilogue when it is a
 // 32-wide-tile o64 / o128 kernel over exactly 32 groups of 2 / 4 channels.  *plan: that instance on the statistics
@@ -433,21 +391,17 @@ static bool x3_gn_hg4(int dtype, int n, int h, int w_, int cin_p, int cout_p, in
   return true;
 }
 static int64_t x3_gn_tiles(int ho, int wo, int cout_p) { return ceil_div(wo, 32) * ceil_div(ho, x3_gn_th(cout_p)); }
-// default on: the statistics epilogue of the non-persistent hg4 costs less than the separate f32 pass saves
-static bool x3_gn_requested(int fuse_mode) {
-  static const bool x3_env = knob("IC2_X3_GN", 1) == 1;  // A/B: 0 = the separate statistics pass by default
-  return fuse_mode > 0 || (fuse_mode < 0 && x3_env);
-}
+// on unless refused (fuse_mode 0): the statistics epilogue of the non-persistent hg4 costs less than the separate f32
+// pass saves
+static bool x3_gn_requested(int fuse_mode) { return fuse_mode != 0; }
 // fused hconv instances: 32 groups over all cout_p channels (VGGBlock: GroupNorm(min(32, c), c) with c = 32 / 64).
-// Off by default: measured on MI355X the epilogue reduction (two extra barriers per tile in the persistent
-// kernel) costs what the saved read of y gains -- C4 357.1 -> 356.7 img/s, C2 1277 -> 1256 (profiles/
-// r2b_conv_gn_ab.txt); knob IC2_CONV_GN=1 enables it.  The statistics epilogue exists for the bf16 halo conv only
-// (hconv_eligible also admits f16 operands)
+// Off unless asked for (fuse_mode > 0): measured on MI355X the epilogue reduction (two extra barriers per tile in the
+// persistent kernel) costs what the saved read of y gains -- C4 357.1 -> 356.7 img/s, C2 1277 -> 1256 (profiles/
+// r2b_conv_gn_ab.txt).  The statistics epilogue exists for the bf16 halo conv only (hconv_eligible also admits f16
+// operands)
 static bool hconv_gn_fuses(int dtype, int64_t M, int cin_p, int cout_p, int cout_valid, int kh, int kw, int groups,
                            int fuse_mode) {
-  static const bool fuse_env = knob("IC2_CONV_GN", 0) == 1;
-  const bool fuse_req = fuse_mode < 0 ? fuse_env : fuse_mode > 0;
-  return fuse_req && dtype == IC2_BF16 && hconv_eligible(dtype, M, cin_p, cout_p, kh, kw) && groups == 32 &&
+  return fuse_mode > 0 && dtype == IC2_BF16 && hconv_eligible(dtype, M, cin_p, cout_p, kh, kw) && groups == 32 &&
          cout_valid == cout_p;
 }
 

@@ -52,6 +52,48 @@ void launch_hg4(IgemmArgs a, const H4Plan& p, bool f16, bool gn_stats, hipStream
 void launch_hconv(const IgemmArgs& a, bool gn_stats, bool f16, hipStream_t s);                      // hconv.hip
 void launch_torgb(const IgemmArgs& a, bool f16, hipStream_t s);                                     // hconv.hip
 
+// conv_dispatch.hip: what the two conv entry points (ic2_conv_igemm_ws, ic2_conv_wino in wino.hip) share.  A ConvCall
+// is the entry point's arguments; conv_check_call runs the checks both make (error texts under the entry's name `who`)
+// and decodes the input-layout bits of `act` and the IEEE flavour of an f16 output; conv_for_chunks then hands `launch`
+// the launch arguments of each chunk of whole images (conv_chunk_n), all of them in one chunk as a rule.
+struct ConvCall {
+  const void *x, *w;
+  void* y;
+  const float *oscale, *bias;
+  int dtype, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, ho, wo;
+  int act;  // as passed: IC2_ACT_IN_LAYOUT bits above the activation; the activation alone after conv_check_call
+  float slope, act_gain, clamp, out_mul;
+  int out_layout;
+  bool in_blocked;  // set by conv_check_call: channel-blocked (NHWC16) input
+  int out_ieee;     // set by conv_check_call: out_dtype was IC2_F16_IEEE (out_dtype becomes IC2_F16)
+};
+int conv_check_call(const char* who, ConvCall& c);
+int conv_chunk_n(int dtype, int n, int h, int w_, int cin_p);
+int64_t conv_x_img_bytes(int dtype, int h, int w_, int cin_p);
+IgemmArgs make_igemm_args(const void* x, const void* w, void* y, const float* bias, int dtype, int out_dtype, int n,
+                          int h, int w_, int cin_p, int cout_p, int cout_valid, int kh, int kw, int pad, float out_mul);
+template <class Launch>
+int conv_for_chunks(const ConvCall& c, Launch&& launch) {
+  const int nc = conv_chunk_n(c.dtype, c.n, c.h, c.w_, c.cin_p);
+  const int64_t x_img = conv_x_img_bytes(c.dtype, c.h, c.w_, c.cin_p);
+  const int64_t y_img = c.out_layout == IC2_LAYOUT_NCHW
+                            ? (int64_t)c.cout_valid * c.ho * c.wo * 4
+                            : (int64_t)c.ho * c.wo * c.cout_p * (c.out_dtype == IC2_F32 ? 4 : 2);
+  for (int n0 = 0; n0 < c.n; n0 += nc) {
+    IgemmArgs a = make_igemm_args(reinterpret_cast<const char*>(c.x) + n0 * x_img, c.w,
+                                  reinterpret_cast<char*>(c.y) + n0 * y_img, c.bias, c.dtype, c.out_dtype,
+                                  c.n - n0 < nc ? c.n - n0 : nc, c.h, c.w_, c.cin_p, c.cout_p, c.cout_valid, c.kh, c.kw,
+                                  c.pad, c.out_mul);
+    a.oscale = c.oscale ? c.oscale + (int64_t)n0 * c.cout_p : nullptr;
+    a.act = c.act; a.slope = c.slope; a.act_gain = c.act_gain; a.clamp = c.clamp;
+    a.out_layout = c.out_layout; a.out_ieee = c.out_ieee;
+    ig_set_input_layout(a, c.in_blocked);
+    const int rc = launch(a);
+    if (rc != IC2_OK) return rc;
+  }
+  return IC2_OK;
+}
+
 // conv_dispatch.hip: conv (bias only, NHWC out) with the GroupNorm partial sums fused into the halo kernels' epilogue
 // when the plan picks one that carries them.  conv_gn_fused returns the number of per-image tiles written to `part`
 // ([n][groups][tiles][2] f64), 0 when the conv ran unfused (the caller then computes the statistics itself), -1 on

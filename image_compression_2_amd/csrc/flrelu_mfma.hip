@@ -415,12 +415,6 @@ __device__ __forceinline__ void fm_quad_transpose(uint2 (&v)[4], int p) {
   }
 }
 
-// diagnostic builds only (tools/build_abl.sh, wrong results): IC2_FM3_ABL bit 0 skips the ring waits, bit 1 the ring
-// DMAs, bit 2 the horizontal pass, bit 3 the vertical up, bit 4 the vertical down, bit 5 the two in-block barriers,
-// bit 6 the output stores (issued to the dropped offset: same instructions, no bytes)
-#ifndef IC2_FM3_ABL
-#define IC2_FM3_ABL 0
-#endif
 // BLK: channel-blocked NHWC16 output [n][c_p/16][out_h][out_w][16] (the hand-off to a conv that reads it blocked).  A
 // wave then owns the 4 adjacent output columns 4 wave .. 4 wave + 3 (instead of wave + NW i) and transposes the 4
 // columns x 4 rows held by each lane quad before the store, so the 16 lanes (4 columns x 4 channel quads) of one row
@@ -623,7 +617,7 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
           const uint32_t off =
               (gy < a.out_h && gx < a.out_w) ? (uint32_t)((gy * a.out_w + gx) * 32 + 16 * (g >> 1)) : FM_OOB;
           const v4u32_t q = {x[0], y[0], x[1], y[1]};
-          __builtin_amdgcn_raw_buffer_store_b128(q, ors, (IC2_FM3_ABL & 64) ? FM_OOB : off, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(q, ors, off, 0, 0);
         }
         return;
       }
@@ -634,7 +628,7 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
         const uint32_t off =
             (gy < a.out_h && gx < a.out_w) ? (uint32_t)(((gy * a.out_w + gx) * a.c_p + 4 * g) * 2) : FM_OOB;
         const uint2 v = fm_out4(a.out_f16, acc_a[i][0] * ps[0], acc_a[i][1] * ps[1], acc_a[i][2] * ps[2], acc_a[i][3] * ps[3]);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, v), ors, (IC2_FM3_ABL & 64) ? FM_OOB : off, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, v), ors, off, 0, 0);
       }
     };
     // grid block k of the item: vertical up (ring -> V), horizontal up / activation / down (V -> D), vertical down
@@ -642,7 +636,7 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
     // finishes acc_a and starts acc_b for the next tile.  A finished tile is stored at the end of its even block.
     auto block = [&](int k, auto mode_c) __attribute__((always_inline)) {
       constexpr int MODE = decltype(mode_c)::value;
-      if constexpr (!(IC2_FM3_ABL & 8)) {
+      {  // vertical up
         constexpr int NC = (NINX + NW - 1) / NW;
         // column x = wave + NW i: one per-lane base per block and immediate offsets.  Columns past NINX - 1 (the
         // last round's surplus waves) read in-bounds bytes of the ring and are not stored
@@ -664,15 +658,15 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
           if (i < NC - 1 || wave + NW * i < NINX)
             *reinterpret_cast<uint2*>(vp + i * NW * 8) = fm_pack4(vt[i][0], vt[i][1], vt[i][2], vt[i][3]);
       }
-      if constexpr (!(IC2_FM3_ABL & 32)) __syncthreads();  // V complete; the ring group k is dead; v-down k-1 done
+      __syncthreads();  // V complete; the ring group k is dead; v-down k-1 done
       // the item's last block: every ring group is dead -> the next item's first rows
       if (k == kend && has_next) load_item(w + gridDim.x);
       // the rows block k+2 needs go out now, into the slot of group k (every wave's vertical up of block k is done):
       // they land behind this block's horizontal pass and vertical down and the next block's vertical up
-      const bool dma = !(IC2_FM3_ABL & 2) && k + 2 <= kend;
+      const bool dma = k + 2 <= kend;
       if (dma) load_group(n, iy0, sx0, c0, k + U + 1);
 #pragma unroll
-      for (int rr = 0; rr < ((IC2_FM3_ABL & 4) ? 0 : RR); ++rr) {
+      for (int rr = 0; rr < RR; ++rr) {
         const int row = wave + NW * rr;
         fm_s4 vb[NBX];
 #pragma unroll
@@ -724,7 +718,7 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
           *reinterpret_cast<uint2*>(d_img + row * G::D_PITCH + (16 * ob + li) * G::D_XP + 2 * g) =
               fm_pack4(d[ob][0], d[ob][1], d[ob][2], d[ob][3]);
       }
-      if (!(IC2_FM3_ABL & 1) && k >= 1 && k < kend) {
+      if (k >= 1 && k < kend) {
         // block k-1's ring DMA must have landed (block k+1 reads it); younger, and left in flight: the stores of the
         // tile finished at the end of block k-1 (odd k >= 3: exactly NST) and this block's own DMA (this wave's
         // share, uniform)
@@ -741,8 +735,8 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
           else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         }
       }
-      if constexpr (!(IC2_FM3_ABL & 32)) __syncthreads();  // D complete; every wave's horizontal reads of V are done
-      if constexpr (!(IC2_FM3_ABL & 16)) {
+      __syncthreads();  // D complete; every wave's horizontal reads of V are done
+      {  // vertical down
         // output column of accumulator i: wave + NW i, or 4 wave + i (BLK).  Either way one read instruction takes one
         // column, so its lanes differ only in (row 4 g + tq, quad tp): the bank pattern D_PITCH was chosen for
         fm_s4 da[OCW];

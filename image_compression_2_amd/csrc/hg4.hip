@@ -36,17 +36,6 @@ struct H4 {
 };
 __device__ __forceinline__ int h4_off(int row, int chunk) { return row * 64 + ((chunk ^ (((row >> 2) & 1) << 1)) << 4); }
 
-// diagnostic builds only (tools/build_abl.sh hg4, wrong results): IC2_HG4_ABL bit 0 skips the multi-tap loop's
-// per-step DMA waits, bit 1 its barrier, bit 2 its fragment reads after the first step, bit 3 its MFMAs, bit 4 its
-// weight DMAs after the first step
-#ifndef IC2_HG4_ABL
-#define IC2_HG4_ABL 0
-#endif
-// IC2_HG4_PAIR=0 (diagnostic builds): the split-weight f16 statistics-epilogue kernels in the plain K order
-#ifndef IC2_HG4_PAIR
-#define IC2_HG4_PAIR 1
-#endif
-
 // HB: the next block's halo is issued as one burst at the block's first tap, every wave exactly HPW DMAs (the ones
 // past the halo into a 1-KiB dummy slot), so no per-tap selection of a halo-offset register (a uniform branch
 // chain, ~60 SALU per step) and a wait count that depends only on the tap
@@ -182,19 +171,16 @@ __device__ __forceinline__ void hg4_body(const IgemmArgs& a, int tiles_x, int ti
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((L - 1) * TPB * NWI) : "memory");  // halo 0 and step 0's slabs landed
     bf16x8 af[TPB][I], bfr[TPB][J];
     for (int s = 0; s < nst; ++s) {
-      if constexpr (!(IC2_HG4_ABL & 2)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       const int t0 = TPB * s;
-      if (!(IC2_HG4_ABL & 16) || s == 0) {
 #pragma unroll
-        for (int u = 0; u < TPB; ++u) issue_w(t0 + u + TPB * L);
-      }
+      for (int u = 0; u < TPB; ++u) issue_w(t0 + u + TPB * L);
       const bool burst = burst_at(s);  // first read >= 3 steps later
       if (burst) issue_hb(t0 / SPB + 1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int u = 0; u < TPB; ++u) {
-        if ((IC2_HG4_ABL & 4) && s > 0) break;
         const int t = t0 + u;
         int hbk, cb, tap;
         step_of(t, hbk, cb, tap);
@@ -218,10 +204,7 @@ __device__ __forceinline__ void hg4_body(const IgemmArgs& a, int tiles_x, int ti
 #pragma unroll
             for (int i = 0; i < I; ++i)
 #pragma unroll
-              for (int j = 0; j < J; ++j) {
-                if constexpr (IC2_HG4_ABL & 8) asm volatile("" ::"v"(af[u][i]), "v"(bfr[PAIR ? 0 : u][j]));
-                else acc[i][j] = mfma32<F16>(af[u][i], bfr[PAIR ? 0 : u][j], acc[i][j]);
-              }
+              for (int j = 0; j < J; ++j) acc[i][j] = mfma32<F16>(af[u][i], bfr[PAIR ? 0 : u][j], acc[i][j]);
           }
         }
       }
@@ -230,10 +213,8 @@ __device__ __forceinline__ void hg4_body(const IgemmArgs& a, int tiles_x, int ti
       // step s+1's slabs landed (issued at step s+1-L); a burst of the last L steps may stay in flight (issued after
       // its step's slabs; bursts are >= 3 steps apart)
       const bool recent = burst || (L > 1 && s > 0 && burst_at(s - 1));
-      if constexpr (!(IC2_HG4_ABL & 1)) {
-        if (recent) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((L - 1) * TPB * NWI + HPW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((L - 1) * TPB * NWI) : "memory");
-      }
+      if (recent) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((L - 1) * TPB * NWI + HPW) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((L - 1) * TPB * NWI) : "memory");
     }
   } else {
 #pragma unroll
@@ -392,17 +373,12 @@ IC2_HG4_KERNEL(hg4_o64_w16_s4_kernel, 4, 4, 1, 4, 16, 4)   // 64 o x (16 x 16) p
                                                                                                 int tx, int ty) { \
     hg4_body<I, J, WGO, WGP, TW, NS, true, true, TPB>(a, tx, ty);                                                \
   }
-// 32-wide tiles: halo burst + several taps per barrier (two for o128 / o192, whose 4-slab ring and double halo
-// fill the 80 KB; three for o64 with a 6-slab ring, one barrier per kernel row), profiles/r3_hg4_taps_ab.txt
+// 32-wide tiles: halo burst + several taps per barrier (two for o96 and for o128, whose 4-slab ring and double
+// halo fill the 80 KB; three for o64 with a 6-slab ring, one barrier per kernel row), profiles/r3_hg4_taps_ab.txt
 IC2_HG4_KERNEL_P(hg4_o128_w32_p2_kernel, 8, 4, 1, 4, 32, 4, 2)  // 128 o x (8 x 32) px
-IC2_HG4_KERNEL_P(hg4_o192_w32_p2_kernel, 6, 4, 2, 2, 32, 4, 2)  // 192 o x (4 x 32) px
 IC2_HG4_KERNEL_P(hg4_o64_w32_p3_kernel, 4, 4, 1, 4, 32, 6, 3)   // 64 o x (8 x 32) px
 IC2_HG4_KERNEL_P(hg4_o96_w32_p2_kernel, 6, 4, 1, 4, 32, 4, 2)   // 96 o x (8 x 32) px
 // the split-bf16 encoder's 64- / 128-wide convs with the GroupNorm statistics of their f32 output in the epilogue
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
-hg4_o64_w32_p3_gn_kernel(IgemmArgs a, int tx, int ty) {
-  hg4_body<4, 4, 1, 4, 32, 6, true, false, 3, true>(a, tx, ty);
-}
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 hg4_o128_w32_p2_gn_kernel(IgemmArgs a, int tx, int ty) {
   hg4_body<8, 4, 1, 4, 32, 4, true, false, 2, true>(a, tx, ty);
@@ -412,36 +388,30 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 hg4_o64_w32_t12_gn_kernel(IgemmArgs a, int tx, int ty) {
   hg4_body<4, 6, 1, 4, 32, 4, true, false, 2, true>(a, tx, ty);
 }
-// the same three with f16 operands: the split encoder's first blocks (IC2_F16X2: f16 input, [hi | lo] f16 weights),
-// the two-tap-per-step ones walking each tap's hi / lo K blocks as one step (PAIR)
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
-hg4_o64_w32_p3_gn_kernel_f16(IgemmArgs a, int tx, int ty) {
-  hg4_body<4, 4, 1, 4, 32, 6, true, true, 3, true>(a, tx, ty);
-}
+// the same two with f16 operands: the split encoder's first blocks (IC2_F16X2: f16 input, [hi | lo] f16 weights),
+// walking each tap's hi / lo K blocks as one step (PAIR)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 hg4_o128_w32_p2_gn_kernel_f16(IgemmArgs a, int tx, int ty) {
-  hg4_body<8, 4, 1, 4, 32, 4, true, true, 2, true, IC2_HG4_PAIR>(a, tx, ty);
+  hg4_body<8, 4, 1, 4, 32, 4, true, true, 2, true, true>(a, tx, ty);
 }
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 hg4_o64_w32_t12_gn_kernel_f16(IgemmArgs a, int tx, int ty) {
-  hg4_body<4, 6, 1, 4, 32, 4, true, true, 2, true, IC2_HG4_PAIR>(a, tx, ty);
+  hg4_body<4, 6, 1, 4, 32, 4, true, true, 2, true, true>(a, tx, ty);
 }
 #undef IC2_HG4_KERNEL
 #undef IC2_HG4_KERNEL_P
 
 // The plan's instance (h4_plan, conv_dispatch.hip; its th x tw are the kernel's pixel tile), or with gn_stats the
-// statistics-epilogue kernel of a 32-wide-tile o64 / o128 plan (th 12: the 12-row o64 one).
+// statistics-epilogue kernel of a 32-wide-tile o64 (12-row tiles) / o128 plan.
 // The halo burst on 32-wide tiles (s276a +2.6 %, s276b +3 %, SG3-T-1024 L11 +7 % over spreading the halo DMAs over
 // the first taps, profiles/r2f_hg4_hb.txt); a 4-slab weight ring (+0.5-1 % over 3, profiles/r2e_hg4_sweep.txt)
 void launch_hg4(IgemmArgs a, const H4Plan& p, bool f16, bool gn_stats, hipStream_t s) {
   void (*kern)(IgemmArgs, int, int);
   if (gn_stats) {
-    if (p.bo == 64 && p.th == 12) kern = f16 ? hg4_o64_w32_t12_gn_kernel_f16 : hg4_o64_w32_t12_gn_kernel;
-    else if (p.bo == 64) kern = f16 ? hg4_o64_w32_p3_gn_kernel_f16 : hg4_o64_w32_p3_gn_kernel;
+    if (p.bo == 64) kern = f16 ? hg4_o64_w32_t12_gn_kernel_f16 : hg4_o64_w32_t12_gn_kernel;
     else kern = f16 ? hg4_o128_w32_p2_gn_kernel_f16 : hg4_o128_w32_p2_gn_kernel;
   } else if (p.tw32) {
-    if (p.bo == 192) kern = f16 ? hg4_o192_w32_p2_kernel_f16 : hg4_o192_w32_p2_kernel;
-    else if (p.bo == 128) kern = f16 ? hg4_o128_w32_p2_kernel_f16 : hg4_o128_w32_p2_kernel;
+    if (p.bo == 128) kern = f16 ? hg4_o128_w32_p2_kernel_f16 : hg4_o128_w32_p2_kernel;
     else if (p.bo == 96) kern = f16 ? hg4_o96_w32_p2_kernel_f16 : hg4_o96_w32_p2_kernel;
     else kern = f16 ? hg4_o64_w32_p3_kernel_f16 : hg4_o64_w32_p3_kernel;
   } else {

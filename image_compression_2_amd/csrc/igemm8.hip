@@ -98,7 +98,9 @@ __device__ __forceinline__ void igemm8_body(const IgemmArgs& a) {
   // 256-pixel x cin_p panel once per tap, so the 9 shifted re-reads of a pixel are cin_p / 64 K-tiles apart and
   // the ~32 resident WGs of an XCD cycle ~8 MB through its 4 MB L2 between them (PMC: 5.4x the compulsory HBM
   // bytes on s148).  channel-major (taps innermost, the halo kernels' order) re-reads each 64-channel panel at the
-  // 9 taps back to back.  IC2_IGEMM_KORDER=0 / 1 selects tap- / channel-major.
+  // 9 taps back to back: s148 +3 %, s148b +5 %, s148c +7 %, C2 +2.6 % (profiles/r2f_korder.txt), so the host always
+  // sets a.korder = 1.  The tap-major arm stays: the kernels measured 1-5 % slower without it
+  // (profiles/r11_conv_prune.txt).
   const bool cmaj = a.korder != 0;
   auto advance = [&](Cur c) {
     c.t += 1;

@@ -35,7 +35,7 @@
 //   A flat tile's wrapped blocks are not 16 consecutive rows: part of their reads are 2-way conflicted, counted on
 //   the host by wx_flat_conflicts and weighed by the planner (wx_tile).
 // V is formed in f16 (packed adds, one rounding per add; the CPU emulation tools/wino_emu.py prices the rounding).
-#include "conv_common.h"
+#include "conv_plan.h"
 
 namespace ic2 {
 
@@ -83,30 +83,6 @@ __device__ __forceinline__ bool wx_slot(const IgemmArgs& a, int b, int fr, int& 
   return r < a.wx_th && t < a.wx_twp;
 }
 
-// diagnostic builds only (wrong results; tools/build_abl.sh wino): IC2_WX_ABL bit 0 skips the U DMAs after the first
-// channel block, bit 1 the section barriers, bit 2 the input-fragment reads, bit 3 the MFMAs, bit 4 the DMA waits
-#ifndef IC2_WX_ABL
-#define IC2_WX_ABL 0
-#endif
-// diagnostic build IC2_WX_STAMP=1 (tools/build_abl.sh winostamp): s_memtime stamps around the sections, summed per
-// wave over the K loop and stored to a.ws[(block * 8 + wave) * 8 + k] as u64 (the launch passes a buffer there):
-// 0 R reads + V, 1 R DMA issue, 2 vmcnt wait, 3 barrier after R + lgkmcnt, 4 M issue, 5 barrier after M, 6 loop
-#ifndef IC2_WX_STAMP
-#define IC2_WX_STAMP 0
-#endif
-// schedule variants (A/B): 0 = reads, V, then DMAs in R; 1 = DMAs first in R; 2 = DMAs first, and the next step's
-// input fragments read inside the second M section of the step (halo DMAs one section later to keep the WAR distance).
-// (Round 6 also tried the next section's A fragments read inside this section's M section, right behind the MFMAs that
-// consumed their registers, with and without the input fragments: level / 2-3 % slower, profiles/r6_schedule_ab.txt.)
-#ifndef IC2_WX_SCHED
-#define IC2_WX_SCHED 0
-#endif
-// wave priority A/B (diagnostic builds, tools/build_abl.sh winoprio): 0 = s_setprio 1 over the M section's MFMAs
-// (default), 1 = no s_setprio, 2 = s_setprio 1 over the R section (reads, V adds, DMA issue) instead
-#ifndef IC2_WX_PRIO
-#define IC2_WX_PRIO 0
-#endif
-
 __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[WX_LDS];
   char* const wsl = lds;
@@ -118,13 +94,13 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
   const int pg = wid & 3;     // pairs 32 pg .. 32 pg + 31
   const int fr = lane & 15, fh = lane >> 4;
 
-  // logical tile -> (o-tile, pixel tile): the o-tiles run in groups of a.group (fastest within a group), each group
-  // over all pixel tiles; the XCD remap hands every XCD a contiguous range, so its L2 holds the U slabs of one group
+  // logical tile -> (o-tile, pixel tile): o-tile-major, each o-tile over all pixel tiles; the XCD remap hands every
+  // XCD a contiguous range, so its L2 streams one o-tile's U slabs (1.5 MiB at 512 channels; the input halos are read
+  // by tiles_o XCDs instead of one)
   const int logical = xcd_remap(blockIdx.x, a.nblocks);
-  const int per_group = a.group * (a.nblocks / a.tiles_o);
-  const int gi = logical / per_group, grem = logical - gi * per_group;
-  const int o_tile = gi * a.group + grem % a.group;
-  int pt = grem / a.group;
+  const int tiles_p = a.nblocks / a.tiles_o;
+  const int o_tile = logical / tiles_p;
+  int pt = logical - o_tile * tiles_p;
   const int tx = pt % a.wx_tx;
   pt /= a.wx_tx;
   const int ty = pt % a.wx_ty;
@@ -244,18 +220,17 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
   // last read by the d(3cb+2) prefetch at section 3).  A wave's DMAs of section r are complete by the end of its
   // section r+3; a half-slab / halo DMA is first read >= 5 sections after it is issued.  vmcnt at the end of block
   // section j = this wave's DMAs of sections j-2 .. j: 9 8 7 6 7 8.
+  // (Measured and not kept: the DMAs ahead of the reads in R, the next step's input or A fragments read inside the M
+  // section behind the MFMAs that consumed their registers -- level / 2-3 % slower, profiles/r6_schedule_ab.txt -- and
+  // s_setprio 1 over the R section or nowhere instead of over the M section's MFMAs.)
   issue_hp(0, 0);
   issue_hp(0, 1);
   issue_hp(0, 2);
 #pragma unroll
   for (int j = 0; j < 5; ++j) issue_hs(0, j);
   issue_hp(1, 0);
-  if constexpr (IC2_WX_SCHED == 2) {
-    asm volatile("s_waitcnt vmcnt(5)" ::: "memory");  // halo 0, half-slabs 0-2 landed (3, 4, halo 1 p0 in flight)
-  } else {
-    issue_hp(1, 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");  // halo 0, half-slabs 0-2 landed (3, 4, halo 1 p0-1 in flight)
-  }
+  issue_hp(1, 1);
+  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");  // halo 0, half-slabs 0-2 landed (3, 4, halo 1 p0-1 in flight)
   __builtin_amdgcn_s_barrier();
   read_d(hal);
   bf16x8 af[2][4];
@@ -266,16 +241,6 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
   if (half == 1) __builtin_amdgcn_s_barrier();  // waves 4-7 run one barrier behind
   __builtin_amdgcn_sched_barrier(0);
 
-  uint64_t st[7] = {0, 0, 0, 0, 0, 0, 0};
-  uint64_t t_prev = 0, t_loop = 0;
-  auto stamp = [&](int k) {
-    if constexpr (IC2_WX_STAMP) {
-      const uint64_t t = __builtin_amdgcn_s_memtime();
-      st[k] += t - t_prev;
-      t_prev = t;
-    }
-  };
-  if constexpr (IC2_WX_STAMP) t_loop = t_prev = __builtin_amdgcn_s_memtime();
   for (int cb = 0; cb < CB; ++cb) {
     const char* hb_cur = hal + (cb & 1) * WX_HALO;
     const char* hb_nxt = hal + ((cb + 1) & 1) * WX_HALO;
@@ -283,88 +248,36 @@ __global__ void __launch_bounds__(512, 1) wino_fx_f16_kernel(IgemmArgs a) {
     for (int j = 0; j < 6; ++j) {
       const int ky = j >> 1, hx = j & 1;
       const char* wl = wsl + j * (WX_SLAB / 2) + aoff;
-      // ---- R section
-      auto r_dma = [&]() {
-        if (!(IC2_WX_ABL & 1) || cb == 0) issue_hs(cb + (j + 5) / 6, (j + 5) % 6);
-        if constexpr (IC2_WX_SCHED == 2) {
-          if (j == 0) issue_hp(cb + 1, 1);
-          if (j == 1) issue_hp(cb + 1, 2);
-          if (j == 5) issue_hp(cb + 2, 0);
-        } else {
-          if (j == 0) issue_hp(cb + 1, 2);
-          if (j >= 4) issue_hp(cb + 2, j - 4);
-        }
-      };
-      if constexpr (IC2_WX_PRIO == 2) __builtin_amdgcn_s_setprio(1);
-      if constexpr (IC2_WX_SCHED >= 1) r_dma();
+      // ---- R section: reads and V, then this wave's DMAs
       if (hx == 0) make_v();
       read_a(wl, 0);
       read_a(wl, 1);
-      if (hx == 1 && IC2_WX_SCHED < 2) {
-        if constexpr (!(IC2_WX_ABL & 4)) read_d(ky < 2 ? hb_cur + (ky + 1) * ky_step : hb_nxt);
-      }
-      if constexpr (IC2_WX_STAMP) {
-        __builtin_amdgcn_sched_barrier(0);
-        stamp(0);
-      }
-      if constexpr (IC2_WX_SCHED == 0) r_dma();
+      if (hx == 1) read_d(ky < 2 ? hb_cur + (ky + 1) * ky_step : hb_nxt);
+      issue_hs(cb + (j + 5) / 6, (j + 5) % 6);
+      if (j == 0) issue_hp(cb + 1, 2);
+      if (j >= 4) issue_hp(cb + 2, j - 4);
       __builtin_amdgcn_sched_barrier(0);
-      stamp(1);
-      if constexpr (!(IC2_WX_ABL & 16)) {
-        if constexpr (IC2_WX_SCHED == 2) {  // halo DMAs at sections 5, 0, 1: 8 9 8 7 6 7
-          if (j == 1) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-          if (j == 0 || j == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-          if (j == 3 || j == 5) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-          if (j == 4) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        } else {
-          if (j == 0) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-          if (j == 1 || j == 5) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-          if (j == 2 || j == 4) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-          if (j == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        }
-      }
-      stamp(2);
-      if constexpr (!(IC2_WX_ABL & 2)) __builtin_amdgcn_s_barrier();
+      if (j == 0) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+      if (j == 1 || j == 5) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      if (j == 2 || j == 4) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
+      if (j == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
-      stamp(3);
       // ---- M section
-      if constexpr (IC2_WX_PRIO == 0) __builtin_amdgcn_s_setprio(1);
-      if constexpr (IC2_WX_PRIO == 2) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int nl = 0; nl < 2; ++nl) {
+      for (int nl = 0; nl < 2; ++nl)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int jb = 0; jb < 2; ++jb) {
-            if constexpr (IC2_WX_ABL & 8) asm volatile("" ::"v"(af[nl][i]), "v"(v[nl][jb]));
-            else
-              acc[nl][4 * hx + i][jb] =
-                  mfma32<true>(af[nl][i], __builtin_bit_cast(bf16x8, v[nl][jb]), acc[nl][4 * hx + i][jb]);
-          }
-        if (IC2_WX_SCHED == 2 && hx == 1 && nl == 0) {  // the next step's input fragments behind the MFMAs
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (!(IC2_WX_ABL & 4)) read_d(ky < 2 ? hb_cur + (ky + 1) * ky_step : hb_nxt);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      if constexpr (IC2_WX_PRIO == 0) __builtin_amdgcn_s_setprio(0);
+          for (int jb = 0; jb < 2; ++jb)
+            acc[nl][4 * hx + i][jb] =
+                mfma32<true>(af[nl][i], __builtin_bit_cast(bf16x8, v[nl][jb]), acc[nl][4 * hx + i][jb]);
+      __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (IC2_WX_STAMP) {  // the MFMAs issued (the last one still in the pipe)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-      stamp(4);
-      if constexpr (!(IC2_WX_ABL & 2)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      stamp(5);
-    }
-  }
-  if constexpr (IC2_WX_STAMP) {
-    st[6] = __builtin_amdgcn_s_memtime() - t_loop;
-    if (lane == 0) {
-      uint64_t* o = reinterpret_cast<uint64_t*>(a.ws) + ((int64_t)blockIdx.x * 8 + wid) * 8;
-#pragma unroll
-      for (int k = 0; k < 7; ++k) o[k] = st[k];
     }
   }
   if (half == 0) __builtin_amdgcn_s_barrier();  // balance the waves 4-7 offset barrier
@@ -614,26 +527,9 @@ static WxTile wx_tile(int n, int ho, int wo, int cout_p) {
   return t;
 }
 
-static int wx_chunk_n(int n, int h, int w_, int cin_p) {
-  const int64_t per_img = (int64_t)h * w_ * cin_p * 2;
-  if ((int64_t)n * per_img < (int64_t)kOob || per_img >= (int64_t)kOob) return n;
-  const int64_t c = ((int64_t)kOob - 1) / per_img;
-  return (int)ceil_div(n, ceil_div(n, c));
-}
-
-static void* g_wx_stamp = nullptr;  // diagnostic stamp buffer (IC2_WX_STAMP builds)
-static int64_t g_wx_stamp_bytes = 0;
-
 }  // namespace ic2
 
 using namespace ic2;
-
-extern "C" int ic2_conv_wino_stamps(void* buf, int64_t bytes) {
-  IC2_CHECK_ARG(IC2_WX_STAMP, "conv_wino_stamps: not a stamp build (IC2_WX_STAMP)");
-  g_wx_stamp = buf;
-  g_wx_stamp_bytes = bytes;
-  return IC2_OK;
-}
 
 extern "C" int ic2_pack_weight_wino(const float* w, int cout, int cin, int cout_p, int cin_p, int prenorm,
                                     float scale, void* u_out, int dtype, void* stream) {
@@ -647,22 +543,19 @@ extern "C" int ic2_pack_weight_wino(const float* w, int cout, int cin, int cout_
 
 // Where the Winograd kernel beats the direct implicit GEMM (tools/bench_wino.py, f16 at batch 32): the >= 256-wide
 // convs on >= 50-pixel outputs (SG3-T-256 L4-L10: 1.10-1.18x); the 38-pixel L0-L3 (tiles pad the 19-pair rows) and
-// the <= 192-wide L11-L13 (hg4) stay direct.  IC2_WINO=0 / 2 (dev knob): never / wherever legal.
+// the <= 192-wide L11-L13 (hg4) stay direct.
 extern "C" int ic2_conv_wino_preferred(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw,
                                        int pad) {
-  static const int mode = knob("IC2_WINO", 1);
   const int ho = h + 2 * pad - kh + 1, wo = w_ + 2 * pad - kw + 1;
   const bool legal = dtype == IC2_F16 && kh == 3 && kw == 3 && n > 0 && ho > 0 && wo > 0 && cin_p % 32 == 0 &&
                      cout_p % 32 == 0 && (int64_t)cout_p * 12 * cin_p * 2 < (int64_t)kOob;
-  if (!legal || mode == 0) return 0;
-  if (mode == 2) return 1;
-  return cin_p >= 256 && cout_p >= 256 && ho >= 50 && wo >= 50;
+  return legal && cin_p >= 256 && cout_p >= 256 && ho >= 50 && wo >= 50;
 }
 
 extern "C" const char* ic2_conv_wino_plan(int n, int h, int w_, int cin_p, int cout_p, int pad) {
   const int ho = h + 2 * pad - 2, wo = w_ + 2 * pad - 2;
   if (n <= 0 || ho <= 0 || wo <= 0 || cin_p <= 0 || cin_p % 32 || cout_p <= 0 || cout_p % 32) return "invalid";
-  const WxTile t = wx_tile(wx_chunk_n(n, h, w_, cin_p), ho, wo, cout_p);
+  const WxTile t = wx_tile(conv_chunk_n(IC2_F16, n, h, w_, cin_p), ho, wo, cout_p);
   static thread_local char buf[64];
   snprintf(buf, sizeof(buf), "wino_fx_o128_p%dx%d%s_f16", t.twp, t.th, t.flat ? "w" : "");  // w: a flat (wrapping) tile
   return buf;
@@ -674,66 +567,19 @@ extern "C" int ic2_conv_wino(const void* x, const void* u, void* y, int dtype, i
                              int out_layout, void* stream) {
   IC2_CHECK_ARG(x && u && y, "conv_wino: null pointer");
   IC2_CHECK_ARG(dtype == IC2_F16, "conv_wino: f16 operands only (dtype %d)", dtype);
-  // the input layout rides in the bits above the activation (ic2ops.h IC2_ACT_IN_LAYOUT)
-  const int act_flags = act, in_layout = IC2_ACT_IN_LAYOUT_OF(act_flags);
-  act = IC2_ACT_OF(act_flags);
-  IC2_CHECK_ARG(in_layout == IC2_LAYOUT_NHWC || in_layout == IC2_LAYOUT_NHWC16, "conv_wino: bad input layout %d",
-                in_layout);
-  const bool in_blocked = in_layout == IC2_LAYOUT_NHWC16;
-  IC2_CHECK_ARG(out_dtype == IC2_F32 || out_dtype == IC2_BF16 ||
-                    ((out_dtype == IC2_F16 || out_dtype == IC2_F16_IEEE) && out_layout != IC2_LAYOUT_NCHW),
-                "conv_wino: bad out dtype %d", out_dtype);
-  IC2_CHECK_ARG(cin_p > 0 && cin_p % 32 == 0 && cout_p > 0 && cout_p % 32 == 0,
-                "conv_wino: channel strides must be positive multiples of 32 (cin_p=%d cout_p=%d)", cin_p, cout_p);
-  IC2_CHECK_ARG(n > 0 && h > 0 && w_ > 0 && pad >= 0, "conv_wino: bad geometry");
-  IC2_CHECK_ARG(ho == h + 2 * pad - 2 && wo == w_ + 2 * pad - 2 && ho > 0 && wo > 0,
-                "conv_wino: output size %dx%d does not match input %dx%d, k=3x3, pad=%d", ho, wo, h, w_, pad);
-  IC2_CHECK_ARG(out_layout == IC2_LAYOUT_NHWC || out_layout == IC2_LAYOUT_NHWC16 ||
-                    (out_layout == IC2_LAYOUT_NCHW && out_dtype == IC2_F32 && cout_valid > 0 && cout_valid <= cout_p),
-                "conv_wino: NCHW output needs f32 and 0 < cout_valid <= cout_p (layout %d)", out_layout);
+  ConvCall cc{x, u, y, oscale, bias, dtype, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, 3, 3, pad, ho, wo,
+              act, slope, act_gain, clamp, out_mul, out_layout};
+  if (const int rc = conv_check_call("conv_wino", cc)) return rc;
   IC2_CHECK_ARG(((uintptr_t)oscale | (uintptr_t)bias) % 16 == 0, "conv_wino: oscale/bias must be 16-byte aligned");
   IC2_CHECK_ARG((int64_t)cout_p * 12 * cin_p * 2 < (int64_t)kOob, "conv_wino: weights too large");
-  const int nc = wx_chunk_n(n, h, w_, cin_p);
-  if (nc < n) {
-    const int64_t x_img = (int64_t)h * w_ * cin_p * 2;
-    const int64_t y_img = out_layout == IC2_LAYOUT_NCHW ? (int64_t)cout_valid * ho * wo * 4
-                                                        : (int64_t)ho * wo * cout_p * (out_dtype == IC2_F32 ? 4 : 2);
-    for (int n0 = 0; n0 < n; n0 += nc) {
-      const int nn = n - n0 < nc ? n - n0 : nc;
-      const int rc = ic2_conv_wino(reinterpret_cast<const char*>(x) + n0 * x_img, u,
-                                   reinterpret_cast<char*>(y) + n0 * y_img, dtype, out_dtype, nn, h, w_, cin_p, cout_p,
-                                   cout_valid, pad, ho, wo, oscale ? oscale + (int64_t)n0 * cout_p : nullptr, bias,
-                                   act_flags, slope, act_gain, clamp, out_mul, out_layout, stream);
-      if (rc != IC2_OK) return rc;
-    }
+  return conv_for_chunks(cc, [&](IgemmArgs& a) -> int {
+    const WxTile t = wx_tile(a.n, ho, wo, cout_p);
+    IC2_CHECK_ARG(t.blocks > 0 && t.blocks < (1LL << 31), "conv_wino: bad tile plan");
+    a.tiles_o = t.to; a.nblocks = (int)t.blocks;
+    a.wx_twp = t.twp; a.wx_th = t.th; a.wx_ns = t.ns; a.wx_hp = t.hp; a.wx_nh = t.nh; a.wx_tx = t.tx; a.wx_ty = t.ty;
+    a.wx_flat = t.flat;
+    hipLaunchKernelGGL(wino_fx_f16_kernel, dim3((unsigned)t.blocks), dim3(64 * WX_NW), 0, as_stream(stream), a);
+    IC2_CHECK_LAUNCH("conv_wino");
     return IC2_OK;
-  }
-  const WxTile t = wx_tile(n, ho, wo, cout_p);
-  IC2_CHECK_ARG(t.blocks > 0 && t.blocks < (1LL << 31), "conv_wino: bad tile plan");
-  const int out_ieee = out_dtype == IC2_F16_IEEE;
-  if (out_ieee) out_dtype = IC2_F16;
-  IgemmArgs a{};
-  a.x = x; a.w = u; a.y = y; a.oscale = oscale; a.bias = bias;
-  a.ws = IC2_WX_STAMP && (int64_t)t.blocks * 8 * 8 * 8 <= g_wx_stamp_bytes ? reinterpret_cast<float*>(g_wx_stamp)
-                                                                          : nullptr;
-  IC2_CHECK_ARG(!IC2_WX_STAMP || a.ws, "conv_wino: stamp build without a large enough ic2_conv_wino_stamps buffer");
-  a.n = n; a.h = h; a.w_ = w_; a.cin_p = cin_p; a.cout_p = cout_p; a.cout_valid = cout_valid;
-  a.kh = 3; a.kw = 3; a.pad = pad; a.ho = ho; a.wo = wo;
-  a.M = n * ho * wo; a.K = 9 * cin_p; a.nq = 3 * (cin_p / 32);
-  // o-tiles per L2 group (1: each XCD streams one o-tile's U, 1.5 MiB at 512 channels; the input halos are read by
-  // tiles_o XCDs instead of one)
-  static const int og_knob = knob("IC2_WINO_OGROUP", 1);
-  int og = og_knob < 1 ? 1 : og_knob > t.to ? t.to : og_knob;
-  while (t.to % og) --og;
-  a.tiles_o = t.to; a.nblocks = (int)t.blocks; a.group = og; a.korder = 1; a.o_base = 0;
-  a.act = act; a.slope = slope; a.act_gain = act_gain; a.clamp = clamp; a.out_mul = out_mul;
-  a.out_layout = out_layout; a.out_dtype = out_dtype; a.out_ieee = out_ieee;
-  a.gn_part = nullptr; a.gn_groups = 0; a.gn_c = 0; a.in_gn = nullptr; a.in_slope = 0.f;
-  a.x_pix = cin_p; a.x_hb32 = 0;
-  ig_set_input_layout(a, in_blocked);
-  a.wx_twp = t.twp; a.wx_th = t.th; a.wx_ns = t.ns; a.wx_hp = t.hp; a.wx_nh = t.nh; a.wx_tx = t.tx; a.wx_ty = t.ty;
-  a.wx_flat = t.flat;
-  hipLaunchKernelGGL(wino_fx_f16_kernel, dim3((unsigned)t.blocks), dim3(64 * WX_NW), 0, as_stream(stream), a);
-  IC2_CHECK_LAUNCH("conv_wino");
-  return IC2_OK;
+  });
 }

@@ -283,10 +283,6 @@ int ic2_conv_wino(const void* x, const void* u, void* y, int dtype, int out_dtyp
  * direct implicit GEMM), else 0.  Host only. */
 int ic2_conv_wino_preferred(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw, int pad);
 
-/* Diagnostic builds only (IC2_WX_STAMP, tools/build_abl.sh winostamp): a device buffer for ic2_conv_wino's per-wave
- * section timestamps (u64 [blocks][8 waves][8]); IC2_E_INVALID in the product build. */
-int ic2_conv_wino_stamps(void* buf, int64_t bytes);
-
 /* ic2_conv_wino's launch plan for a geometry, e.g. "wino_fx_o128_p15x8_f16" (tile: 15 pairs x 8 rows).  Host only. */
 const char* ic2_conv_wino_plan(int n, int h, int w_, int cin_p, int cout_p, int pad);
 
@@ -421,8 +417,8 @@ int ic2_gap_bwd(const float* dpooled, void* dx, int dtype, int n, int hw, int c_
  * stored (rounded) values, so y is not read a second time; otherwise the two-stage statistics pass of
  * ic2_group_norm_stats runs after the conv.  stats: ic2_conv3x3_gn_stats_floats() floats (statistics + partial
  * sums); conv_ws / conv_ws_bytes: the conv's split-K workspace as for ic2_conv_igemm_ws.  fuse: 1 = fused statistics
- * where the halo conv runs, 0 = always the separate pass, -1 = default (separate; env IC2_CONV_GN=1 fuses -- measured
- * at parity on MI355X).  Deterministic.  dtype IC2_BF16X3: the split-bf16 encoder -- x stored
+ * where the halo conv runs, 0 = always the separate pass, -1 = default (separate: the fusion measured at parity on
+ * MI355X).  Deterministic.  dtype IC2_BF16X3: the split-bf16 encoder -- x stored
  * [hi | lo] with cin_p = the tripled (GEMM K) channel count, w from ic2_pack_weight(IC2_BF16X3), y f32 NHWC; the
  * statistics come out of the 4-wave halo GEMM's epilogue (on the f32 values as stored) when it runs a 64- / 128-wide
  * layer with 32 groups (fuse != 0), else the separate pass.  dtype IC2_F16X2: the same with the f16 input and

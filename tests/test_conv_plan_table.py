@@ -74,15 +74,3 @@ def test_planner_matches_recorded_table(swept):
                       f"{rec['gn_fuses'][r]} -> {swept['gn_fuses'][r]}")
     assert len(rows) == 0, f"{len(rows)} of {len(geom)} rows differ (recorded -> now):\n" + "\n".join(report)
 
-
-def test_tail_split_follows_the_tile_group_knob():
-    """The tail split needs p-tile-major tiles (IC2_IGEMM_GROUP = 1): under another group the plan name and the
-    workspace query say what the launch does -- one full-K launch, no workspace."""
-    code = ("import sys; sys.path.insert(0, %r); from image_compression_2_amd import _native as nv; "
-            "print(nv.conv_plan(nv.F16, nv.F16, nv.NHWC16, 32, 36, 36, 512, 512, 512, 3, 3, 2), "
-            "nv.query('ic2_conv_igemm_ws_bytes', nv.F16, 32, 36, 36, 512, 512, 3, 3, 2))" % ROOT)
-    env = {k: v for k, v in os.environ.items() if not k.startswith("IC2_")}
-    env.update(IC2_DEV="1", IC2_IGEMM_GROUP="2")
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    assert r.stdout.split() == ["igemm8_og2_f16", "0"]

@@ -455,13 +455,23 @@ def test_conv_halo_gemm4(cuda, dtype):
 
 
 @pytest.mark.parametrize("dtype", ["torch.bfloat16", "torch.float16"])
-@pytest.mark.parametrize("bo", [96, 192])
-def test_conv_halo_gemm4_o192_outputs(cuda, dtype, bo):
-    """192-wide outputs on either hg4 instance, forced with IC2_HG4_BO in a child process: two 96-wide o-tiles (the
-    default; waves 2-3 issue one weight DMA fewer per tap) or one 192-wide o-tile, against F.conv2d in fp64:
-    181 -> 192 padded outputs, ragged tiles."""
-    _child_conv_cases({"IC2_HG4": "2", "IC2_HG4_BO": str(bo)}, [(128, 181, 40, 2), (256, 192, 31, 2), (64, 192, 30, 1)],
-                      dtype, n=4)
+def test_conv_halo_gemm4_o192_outputs(cuda, dtype):
+    """192-wide outputs on both hg4 forms, hg4 forced with IC2_HG4=2 in a child process: two 96-wide o-tiles on 32-wide
+    pixel tiles (waves 2-3 issue one weight DMA fewer per tap) or one 192-wide o-tile on 16-wide ones, whichever pads
+    the output less, against F.conv2d in fp64: 181 -> 192 padded outputs, ragged tiles.  The plan query, asked in a
+    child under the same environment, must say that the cases still cover both forms."""
+    import subprocess, sys
+    cases = [(128, 181, 40, 2), (256, 192, 31, 2), (64, 192, 30, 1)]
+    dt = {"torch.bfloat16": nv.BF16, "torch.float16": nv.F16}[dtype]
+    code = (f"import sys; sys.path.insert(0, {repr(str(os.getcwd()))}); from image_compression_2_amd import _native as nv\n"
+            f"for cin, cout, size, pad in {cases!r}:\n"
+            f"    print(nv.conv_plan({dt}, {dt}, nv.NHWC, 4, size, size, nv.pad32(cin), nv.pad32(cout), cout, 3, 3, pad))")
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, IC2_DEV="1", IC2_HG4="2"), capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-4000:]
+    f16 = "_f16" if dt == nv.F16 else ""
+    assert r.stdout.split() == ["hg4_o192_w16_s4" + f16, "hg4_o192_w16_s4" + f16, "hg4_o96_w32_p2" + f16], r.stdout
+    _child_conv_cases({"IC2_HG4": "2"}, cases, dtype, n=4)
 
 
 @pytest.mark.parametrize("cin,cout,size,pad,n", [(512, 512, 12, 1, 3), (1024, 320, 9, 1, 2), (768, 256, 7, 2, 5),

@@ -4,7 +4,8 @@
 # (tools/pmc_traffic.sh).  Each GPU step has its own time limit; the script stops at the first failure.
 #   bash tools/gpu_evidence.sh <tag> [tests [K] smoke c2 c4 c5 trace trace5 pmc pmc4]   (default: c2 c4 c5 trace pmc)
 # tests: the GPU pytest suite (optionally only `-k K`, K = comma-separated alternatives), smoke: __graft_entry__.smoke(), pmc4: the C4 PMC traffic,
-# abwino <tag>: the Winograd conv of image_compression_2_amd/libic2ops_<tag>.so (tools/build_abl.sh) against the default
+# abwino <tag>: the Winograd conv of image_compression_2_amd/libic2ops_<tag>.so (a variant built through build_native.py's IC2_BUILD_DIR /
+# IC2_LIB_OUT / IC2_EXTRA_CFLAGS) against the default
 # library -- tests/test_gpu_wino.py on the variant, then tools/bench_wino.py on both, alternating, two rounds;
 # ab <tag> <tests> <shapes>: the same for any variant library, <tests> = comma-separated test files under tests/,
 # <shapes> = comma-separated tools/bench_wino.py shapes (its "direct" column times the implicit-GEMM plan).

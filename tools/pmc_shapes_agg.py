@@ -21,7 +21,7 @@ def is_conv(name):
 
 def dispatches_per_call(ci, co, s, pad, n=32):
     """Conv-body dispatches of one ic2_conv_igemm call: 2 where the launch plan splits an odd multiple of 128
-    output channels (> 128) over the 256-wide and the 128 x 512 8-phase tiles (conv_dispatch.hip, IC2_IGEMM_SPLIT)."""
+    output channels (> 128) over the 256-wide and the 128 x 512 8-phase tiles (conv_dispatch.hip, ConvPlan::split384)."""
     cop = (co + 31) // 32 * 32 if co <= 128 else (co + 63) // 64 * 64
     ho = s + 2 * pad - 2
     m = n * ho * ho
