@@ -42,14 +42,10 @@ struct IgemmArgs {
   int act;
   float slope, act_gain, clamp, out_mul;
   int out_layout, out_dtype;
-  // fused GroupNorm statistics (hconv only; ic2_conv3x3_gn_fwd): per (image, group, tile) f64 (sum, sumsq) of
-  // the stored (rounded) outputs of channels < gn_c; null = off
+  // fused GroupNorm statistics (the hg4 statistics-epilogue kernels of the split modes; ic2_conv3x3_gn_fwd): per
+  // (image, group, tile) f64 (sum, sumsq) of the stored (rounded) outputs of channels < gn_c; null = off
   double* gn_part;
   int gn_groups, gn_c;
-  // GroupNorm + lrelu of the INPUT applied while the halo conv stages it (hconv, cin_p 32 / 64 only): per
-  // (sample, input channel) (mean, rstd * gamma, beta, 0) f32 [n][cin_p][4]; null = the input is used as is
-  const float* in_gn;
-  float in_slope;
   // input storage: x_pix = elements per input pixel (cin_p, or 2/3 of it for the split-bf16 input, stored [hi | lo]
   // while the GEMM's K runs over [hi | hi | lo] against [hi | lo | hi] weights); x_hb32 = 32-channel blocks of the hi
   // part (0: plain storage).  K block b of 32 channels reads stored block ig_xb32(a, b): b, or b - x_hb32 past hi

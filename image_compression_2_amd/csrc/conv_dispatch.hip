@@ -123,8 +123,6 @@ static bool hconv_eligible(int dtype, int64_t M, int cin_p, int cout_p, int kh, 
   return is16(dtype) && kh == 3 && kw == 3 && (cin_p == 32 || cin_p == 64 || cin_p == 96) &&
          (cout_p == 32 || cout_p == 64) && M >= 65536;
 }
-// its TH x 32-pixel tiles per image
-static int64_t hconv_tiles(int cin_p, int ho, int wo) { return ceil_div(wo, 32) * ceil_div(ho, cin_p > 64 ? 4 : 8); }
 
 // (the ToRGB kernel maps output pixel p to input pixel p: 1x1, no padding)
 static bool torgb_eligible(int dtype, int cin_p, int cout_valid, int kh, int kw, int pad, int out_layout,
@@ -344,7 +342,7 @@ extern "C" int ic2_conv_igemm_ws(const void* x, const void* w, void* y, int dtyp
     switch (c.kind) {
       case CK_TORGB: launch_torgb(a, f16, s); break;
       case CK_HG4: launch_hg4(a, c.h4, f16, false, s); break;
-      case CK_HCONV: launch_hconv(a, false, f16, s); break;
+      case CK_HCONV: launch_hconv(a, f16, s); break;
       case CK_IGEMM:
         if (c.tile >= IG_G8_OG2) launch_igemm8(a, c, f16, s);
         else launch_igemm(a, c.tile, f16, c.splits, s);
@@ -366,12 +364,10 @@ extern "C" int ic2_conv_igemm(const void* x, const void* w, void* y, int dtype, 
 
 namespace ic2 {
 // ------------------------------------------------------------------------------------------------
-// conv + GroupNorm statistics (conv_plan.h): the bf16 halo conv (hconv) and, for the split inputs, hg4.
-bool conv_gn_in_supported(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw, int pad) {
-  const int ho = h + 2 * pad - kh + 1, wo = w_ + 2 * pad - kw + 1;
-  if (dtype != IC2_BF16 || cin_p != 64 || ho <= 0 || wo <= 0) return false;
-  return hconv_eligible(dtype, (int64_t)n * ho * wo, cin_p, cout_p, kh, kw);
-}
+// conv + GroupNorm statistics (conv_plan.h): the statistics ride in the hg4 epilogue of the split modes.  The bf16 halo
+// conv (hconv) had such an epilogue too; it was removed because its two extra barriers per tile of the persistent kernel
+// cost what the saved read of y gained (C2 1277 -> 1256 img/s, profiles/r2b_conv_gn_ab.txt), so every other dtype runs
+// the plain conv and the caller the separate statistics pass.
 
 // rows of the statistics-epilogue kernel's pixel tile: 12 for the 64-wide outputs, else 8
 static int x3_gn_th(int cout_p) { return cout_p == 64 ? 12 : 8; }
@@ -394,90 +390,49 @@ static int64_t x3_gn_tiles(int ho, int wo, int cout_p) { return ceil_div(wo, 32)
 // on unless refused (fuse_mode 0): the statistics epilogue of the non-persistent hg4 costs less than the separate f32
 // pass saves
 static bool x3_gn_requested(int fuse_mode) { return fuse_mode != 0; }
-// fused hconv instances: 32 groups over all cout_p channels (VGGBlock: GroupNorm(min(32, c), c) with c = 32 / 64).
-// Off unless asked for (fuse_mode > 0): measured on MI355X the epilogue reduction (two extra barriers per tile in the
-// persistent kernel) costs what the saved read of y gains -- C4 357.1 -> 356.7 img/s, C2 1277 -> 1256 (profiles/
-// r2b_conv_gn_ab.txt).  The statistics epilogue exists for the bf16 halo conv only (hconv_eligible also admits f16
-// operands)
-static bool hconv_gn_fuses(int dtype, int64_t M, int cin_p, int cout_p, int cout_valid, int kh, int kw, int groups,
-                           int fuse_mode) {
-  return fuse_mode > 0 && dtype == IC2_BF16 && hconv_eligible(dtype, M, cin_p, cout_p, kh, kw) && groups == 32 &&
-         cout_valid == cout_p;
-}
+static bool x3_dtype(int dtype) { return dtype == IC2_BF16X3 || dtype == IC2_F16X2; }
 
 bool conv_gn_fuses(int dtype, int n, int h, int w_, int cin_p, int cout_p, int cout_valid, int kh, int kw, int pad,
                    int groups, int fuse_mode) {
-  if (dtype == IC2_BF16X3 || dtype == IC2_F16X2)
-    return x3_gn_requested(fuse_mode) && x3_gn_hg4(dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, groups);
-  const int ho = h + 2 * pad - kh + 1, wo = w_ + 2 * pad - kw + 1;
-  if (ho <= 0 || wo <= 0) return false;
-  return hconv_gn_fuses(dtype, (int64_t)n * ho * wo, cin_p, cout_p, cout_valid, kh, kw, groups, fuse_mode);
+  return x3_dtype(dtype) && x3_gn_requested(fuse_mode) &&
+         x3_gn_hg4(dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, groups);
 }
 
 int conv_gn_fused(const void* x, const void* w, void* y, int dtype, int n, int h, int w_, int cin_p, int cout_p,
                   int cout_valid, int kh, int kw, int pad, const float* bias, int groups, double* part,
-                  int64_t part_doubles, void* workspace, int64_t ws_bytes, int fuse_mode, hipStream_t s,
-                  const float* in_gn, float in_slope, float out_mul) {
+                  int64_t part_doubles, void* workspace, int64_t ws_bytes, int fuse_mode, hipStream_t s, float out_mul) {
   const int ho = h + 2 * pad - kh + 1, wo = w_ + 2 * pad - kw + 1;
-  const int64_t M = (int64_t)n * ho * wo;
-  if (dtype == IC2_BF16X3 || dtype == IC2_F16X2) {
-    // Output f32 (split bf16) / f16 (split-weight f16: its consumer's operand is f16 anyway)
-    const int ydt = dtype == IC2_F16X2 ? IC2_F16 : IC2_F32;
-    if (in_gn != nullptr) {
-      set_error("conv3x3_gnin_gn_fwd: no input GroupNorm fusion in the split modes");
-      return -2;
-    }
-    H4Plan p;
-    int nc = n;
-    const int64_t ntile = x3_gn_tiles(ho, wo, cout_p);  // the statistics kernel's 32-wide tiles per image
-    const bool fuse = x3_gn_requested(fuse_mode) && bias != nullptr && part != nullptr &&
-                      part_doubles >= (int64_t)n * groups * ntile * 2 &&
-                      x3_gn_hg4(dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, groups, &p, &nc);
-    if (!fuse) {
-      const int rc = ic2_conv_igemm_ws(x, w, y, dtype, ydt, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, ho, wo,
-                                       nullptr, bias, 0, 0.f, 1.f, -1.f, out_mul, IC2_LAYOUT_NHWC, workspace,
-                                       ws_bytes, s);
-      return rc == IC2_OK ? 0 : -1;
-    }
-    IgemmArgs a = make_igemm_args(x, w, y, bias, dtype, ydt, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, out_mul);
-    a.gn_groups = groups; a.gn_c = cout_valid;
-    for (int i0 = 0; i0 < n; i0 += nc) {  // chunks of whole images (< 2^31 input bytes per launch)
-      const int cnt = n - i0 < nc ? n - i0 : nc;
-      a.x = reinterpret_cast<const char*>(x) + (int64_t)i0 * h * w_ * a.x_pix * 2;
-      a.y = reinterpret_cast<char*>(y) + (int64_t)i0 * ho * wo * cout_p * (ydt == IC2_F16 ? 2 : 4);
-      a.gn_part = part + (int64_t)i0 * groups * ntile * 2;
-      a.n = cnt;
-      a.M = (int)((int64_t)cnt * ho * wo);
-      launch_hg4(a, p, dtype == IC2_F16X2, true, s);
-    }
-    return (int)ntile;
-  }
-  const int64_t nch = hconv_tiles(cin_p, ho, wo);
-  const bool fuse = hconv_gn_fuses(dtype, M, cin_p, cout_p, cout_valid, kh, kw, groups, fuse_mode) && part != nullptr &&
-                    part_doubles >= (int64_t)n * groups * nch * 2 && bias != nullptr;
-  if (in_gn != nullptr && !conv_gn_in_supported(dtype, n, h, w_, cin_p, cout_p, kh, kw, pad)) {
-    set_error("conv3x3_gn_fwd: input GroupNorm fusion needs the halo conv (bf16, cin_p 64)");
-    return -2;
-  }
-  if (!fuse && in_gn == nullptr) {
-    const int rc = ic2_conv_igemm_ws(x, w, y, dtype, dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, ho, wo,
-                                     nullptr, bias, 0, 0.f, 1.f, -1.f, 1.f, IC2_LAYOUT_NHWC, workspace, ws_bytes, s);
+  // Output of the split modes: f32 (split bf16) / f16 (split-weight f16: its consumer's operand is f16 anyway)
+  const int ydt = dtype == IC2_F16X2 ? IC2_F16 : dtype == IC2_BF16X3 ? IC2_F32 : dtype;
+  H4Plan p;
+  int nc = n;
+  const int64_t ntile = x3_gn_tiles(ho, wo, cout_p);  // the statistics kernel's 32-wide tiles per image
+  const bool fuse = x3_dtype(dtype) && x3_gn_requested(fuse_mode) && bias != nullptr && part != nullptr &&
+                    part_doubles >= (int64_t)n * groups * ntile * 2 &&
+                    x3_gn_hg4(dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, groups, &p, &nc);
+  if (!fuse) {
+    const int rc = ic2_conv_igemm_ws(x, w, y, dtype, ydt, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, ho, wo,
+                                     nullptr, bias, 0, 0.f, 1.f, -1.f, out_mul, IC2_LAYOUT_NHWC, workspace, ws_bytes, s);
     return rc == IC2_OK ? 0 : -1;
   }
-  IgemmArgs a = make_igemm_args(x, w, y, bias, dtype, dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, 1.f);
-  a.gn_part = fuse ? part : nullptr; a.gn_groups = groups; a.gn_c = cout_valid;
-  a.in_gn = in_gn; a.in_slope = in_slope;
-  launch_hconv(a, fuse, false, s);
-  return fuse ? (int)nch : 0;
+  IgemmArgs a = make_igemm_args(x, w, y, bias, dtype, ydt, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, out_mul);
+  a.gn_groups = groups; a.gn_c = cout_valid;
+  for (int i0 = 0; i0 < n; i0 += nc) {  // chunks of whole images (< 2^31 input bytes per launch)
+    const int cnt = n - i0 < nc ? n - i0 : nc;
+    a.x = reinterpret_cast<const char*>(x) + (int64_t)i0 * h * w_ * a.x_pix * 2;
+    a.y = reinterpret_cast<char*>(y) + (int64_t)i0 * ho * wo * cout_p * (ydt == IC2_F16 ? 2 : 4);
+    a.gn_part = part + (int64_t)i0 * groups * ntile * 2;
+    a.n = cnt;
+    a.M = (int)((int64_t)cnt * ho * wo);
+    launch_hg4(a, p, dtype == IC2_F16X2, true, s);
+  }
+  return (int)ntile;
 }
 
 int64_t conv_gn_fused_part_doubles(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw, int pad,
                                    int groups) {
   const int ho = h + 2 * pad - kh + 1, wo = w_ + 2 * pad - kw + 1;
-  if (dtype == IC2_BF16X3 || dtype == IC2_F16X2)
-    return x3_gn_hg4(dtype, n, h, w_, cin_p, cout_p, cout_p, kh, kw, pad, groups)
-               ? (int64_t)n * groups * x3_gn_tiles(ho, wo, cout_p) * 2 : 0;
-  if (dtype != IC2_BF16 || !hconv_eligible(dtype, (int64_t)n * ho * wo, cin_p, cout_p, kh, kw)) return 0;
-  return (int64_t)n * groups * hconv_tiles(cin_p, ho, wo) * 2;
+  return x3_dtype(dtype) && x3_gn_hg4(dtype, n, h, w_, cin_p, cout_p, cout_p, kh, kw, pad, groups)
+             ? (int64_t)n * groups * x3_gn_tiles(ho, wo, cout_p) * 2 : 0;
 }
 }  // namespace ic2

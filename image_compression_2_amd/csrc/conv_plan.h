@@ -49,7 +49,7 @@ void launch_igemm(const IgemmArgs& a, int tile, bool f16, int splits, hipStream_
 void launch_splitk_reduce(const IgemmArgs& a, int splits, int p_lo, hipStream_t s);                 // igemm.hip
 void launch_igemm8(const IgemmArgs& a, const ConvPlan& c, bool f16, hipStream_t s);                 // igemm8.hip
 void launch_hg4(IgemmArgs a, const H4Plan& p, bool f16, bool gn_stats, hipStream_t s);              // hg4.hip
-void launch_hconv(const IgemmArgs& a, bool gn_stats, bool f16, hipStream_t s);                      // hconv.hip
+void launch_hconv(const IgemmArgs& a, bool f16, hipStream_t s);                                     // hconv.hip
 void launch_torgb(const IgemmArgs& a, bool f16, hipStream_t s);                                     // hconv.hip
 
 // conv_dispatch.hip: what the two conv entry points (ic2_conv_igemm_ws, ic2_conv_wino in wino.hip) share.  A ConvCall
@@ -94,15 +94,14 @@ int conv_for_chunks(const ConvCall& c, Launch&& launch) {
   return IC2_OK;
 }
 
-// conv_dispatch.hip: conv (bias only, NHWC out) with the GroupNorm partial sums fused into the halo kernels' epilogue
-// when the plan picks one that carries them.  conv_gn_fused returns the number of per-image tiles written to `part`
-// ([n][groups][tiles][2] f64), 0 when the conv ran unfused (the caller then computes the statistics itself), -1 on
-// an argument error and -2 on an unsupported input-GroupNorm request (message set).
+// conv_dispatch.hip: conv (bias only, NHWC out) with the GroupNorm partial sums fused into the hg4 kernels' epilogue
+// when the plan picks one that carries them (the split modes only).  conv_gn_fused returns the number of per-image
+// tiles written to `part` ([n][groups][tiles][2] f64), 0 when the conv ran unfused (the caller then computes the
+// statistics itself) and -1 on an argument error (message set).  fuse_mode: 0 = never fuse, else the plan's choice.
 int conv_gn_fused(const void* x, const void* w, void* y, int dtype, int n, int h, int w_, int cin_p, int cout_p,
                   int cout_valid, int kh, int kw, int pad, const float* bias, int groups, double* part,
                   int64_t part_doubles, void* workspace, int64_t ws_bytes, int fuse_mode, hipStream_t s,
-                  const float* in_gn, float in_slope, float out_mul = 1.f);
-bool conv_gn_in_supported(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw, int pad);
+                  float out_mul = 1.f);
 bool conv_gn_fuses(int dtype, int n, int h, int w_, int cin_p, int cout_p, int cout_valid, int kh, int kw, int pad,
                    int groups, int fuse_mode);
 int64_t conv_gn_fused_part_doubles(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw, int pad,

@@ -1,6 +1,6 @@
 // HVAE_VGG_Encoder support kernels (/root/reference/stylegan3_hvae_full.py:105-247) and the metric /
 // resize helpers of the compressor API.  All HBM-bound; NHWC with padded channel stride c_p.
-#include "conv_plan.h"  // conv_gn_*: the conv with the GroupNorm partial sums fused into the halo kernels' epilogue
+#include "conv_plan.h"  // conv_gn_*: the conv with the GroupNorm partial sums fused into the hg4 kernels' epilogue
 
 #include <algorithm>
 #include <type_traits>
@@ -351,7 +351,7 @@ __global__ void __launch_bounds__(256) gn_apply_oct_kernel(const TI* __restrict_
       ld8(yb + (int64_t)idx * c_p, v);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        float t = __builtin_fmaf(v[k] - mu[k], sc[k], sh[k]);  // as gn_lrelu_bf16x8 (hconv.hip), bit for bit
+        float t = __builtin_fmaf(v[k] - mu[k], sc[k], sh[k]);  // one rounding (fma)
         t = t < 0.f ? t * slope : t;
         res[k] = accum ? res[k] + t : t;
       }
@@ -658,72 +658,46 @@ __global__ void __launch_bounds__(256) from_rgb_kernel(const float* __restrict__
   }
 }
 
+// The three entry points' shared launch: the argument checks under the entry's name `who`, then the <COUT, X3, H16>
+// instance of cout_p.  wide: the f32-weight kernels (wc = cout <= cout_p) also come 128 wide; the bf16 one (wc = the
+// packed weight's cin_p >= cin) in {32, 64} only.
+template <bool X3, bool H16>
+static int launch_from_rgb(const char* who, const float* x, int cin, const void* w, int wc, const float* bias, void* y,
+                           int n, int h, int w_, int cout_p, void* stream) {
+  IC2_CHECK_ARG(x && w && bias && y && n > 0 && h > 0 && w_ > 0, "%s: null pointer / bad geometry", who);
+  if constexpr (X3)
+    IC2_CHECK_ARG(cin >= 1 && cin <= 4 && wc >= 1 && wc <= cout_p && (cout_p == 32 || cout_p == 64 || cout_p == 128),
+                  "%s: needs 1 <= cin <= 4, cout <= cout_p, cout_p in {32, 64, 128} (cin=%d cout=%d cout_p=%d)", who, cin,
+                  wc, cout_p);
+  else
+    IC2_CHECK_ARG(cin >= 1 && cin <= 4 && wc >= cin && (cout_p == 32 || cout_p == 64),
+                  "%s: needs 1 <= cin <= 4 and cout_p in {32, 64} (cin=%d cout_p=%d)", who, cin, cout_p);
+  IC2_CHECK_ARG((uintptr_t)y % 16 == 0, "%s: output must be 16-byte aligned", who);
+  const int tiles_x = (w_ + 31) / 32, tiles_y = (h + 7) / 8;
+  const int64_t blocks = (int64_t)n * tiles_x * tiles_y;
+  IC2_CHECK_ARG(blocks < (1LL << 31), "%s: too many tiles", who);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), x, cin, w, wc, bias, (bf16_t*)y,
+                       h, w_, tiles_x, tiles_y);
+  };
+  if (cout_p == 32) launch(from_rgb_kernel<32, X3, H16>);
+  else if (cout_p == 64) launch(from_rgb_kernel<64, X3, H16>);
+  else if constexpr (X3) launch(from_rgb_kernel<128, X3, H16>);
+  IC2_CHECK_LAUNCH(who);
+  return IC2_OK;
+}
+
 extern "C" int ic2_from_rgb_conv(const float* x, int cin, const void* w, int cin_p, const float* bias, void* y, int n,
                                  int h, int w_, int cout_p, void* stream) {
-  IC2_CHECK_ARG(x && w && bias && y && n > 0 && h > 0 && w_ > 0, "from_rgb_conv: null pointer / bad geometry");
-  IC2_CHECK_ARG(cin >= 1 && cin <= 4 && cin_p >= cin && (cout_p == 32 || cout_p == 64),
-                "from_rgb_conv: needs 1 <= cin <= 4 and cout_p in {32, 64} (cin=%d cout_p=%d)", cin, cout_p);
-  IC2_CHECK_ARG((uintptr_t)y % 16 == 0, "from_rgb_conv: output must be 16-byte aligned");
-  const int tiles_x = (w_ + 31) / 32, tiles_y = (h + 7) / 8;
-  const int64_t blocks = (int64_t)n * tiles_x * tiles_y;
-  IC2_CHECK_ARG(blocks < (1LL << 31), "from_rgb_conv: too many tiles");
-  hipStream_t s = as_stream(stream);
-  if (cout_p == 32)
-    hipLaunchKernelGGL(from_rgb_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, s, x, cin, w, cin_p, bias,
-                       (bf16_t*)y, h, w_, tiles_x, tiles_y);
-  else
-    hipLaunchKernelGGL(from_rgb_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, s, x, cin, w, cin_p, bias,
-                       (bf16_t*)y, h, w_, tiles_x, tiles_y);
-  IC2_CHECK_LAUNCH("from_rgb_conv");
-  return IC2_OK;
+  return launch_from_rgb<false, false>("from_rgb_conv", x, cin, w, cin_p, bias, y, n, h, w_, cout_p, stream);
 }
-
 extern "C" int ic2_from_rgb_conv_x3(const float* x, int cin, const float* w, int cout, const float* bias, void* y, int n,
                                     int h, int w_, int cout_p, void* stream) {
-  IC2_CHECK_ARG(x && w && bias && y && n > 0 && h > 0 && w_ > 0, "from_rgb_conv_x3: null pointer / bad geometry");
-  IC2_CHECK_ARG(cin >= 1 && cin <= 4 && cout >= 1 && cout <= cout_p && (cout_p == 32 || cout_p == 64 || cout_p == 128),
-                "from_rgb_conv_x3: needs 1 <= cin <= 4, cout <= cout_p, cout_p in {32, 64, 128} (cin=%d cout=%d cout_p=%d)",
-                cin, cout, cout_p);
-  IC2_CHECK_ARG((uintptr_t)y % 16 == 0, "from_rgb_conv_x3: output must be 16-byte aligned");
-  const int tiles_x = (w_ + 31) / 32, tiles_y = (h + 7) / 8;
-  const int64_t blocks = (int64_t)n * tiles_x * tiles_y;
-  IC2_CHECK_ARG(blocks < (1LL << 31), "from_rgb_conv_x3: too many tiles");
-  hipStream_t s = as_stream(stream);
-  if (cout_p == 32)
-    hipLaunchKernelGGL((from_rgb_kernel<32, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, cin, w, cout, bias,
-                       (bf16_t*)y, h, w_, tiles_x, tiles_y);
-  else if (cout_p == 64)
-    hipLaunchKernelGGL((from_rgb_kernel<64, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, cin, w, cout, bias,
-                       (bf16_t*)y, h, w_, tiles_x, tiles_y);
-  else
-    hipLaunchKernelGGL((from_rgb_kernel<128, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, cin, w, cout, bias,
-                       (bf16_t*)y, h, w_, tiles_x, tiles_y);
-  IC2_CHECK_LAUNCH("from_rgb_conv_x3");
-  return IC2_OK;
+  return launch_from_rgb<true, false>("from_rgb_conv_x3", x, cin, w, cout, bias, y, n, h, w_, cout_p, stream);
 }
-
 extern "C" int ic2_from_rgb_conv_f16(const float* x, int cin, const float* w, int cout, const float* bias, void* y, int n,
                                      int h, int w_, int cout_p, void* stream) {
-  IC2_CHECK_ARG(x && w && bias && y && n > 0 && h > 0 && w_ > 0, "from_rgb_conv_f16: null pointer / bad geometry");
-  IC2_CHECK_ARG(cin >= 1 && cin <= 4 && cout >= 1 && cout <= cout_p && (cout_p == 32 || cout_p == 64 || cout_p == 128),
-                "from_rgb_conv_f16: needs 1 <= cin <= 4, cout <= cout_p, cout_p in {32, 64, 128} (cin=%d cout=%d cout_p=%d)",
-                cin, cout, cout_p);
-  IC2_CHECK_ARG((uintptr_t)y % 16 == 0, "from_rgb_conv_f16: output must be 16-byte aligned");
-  const int tiles_x = (w_ + 31) / 32, tiles_y = (h + 7) / 8;
-  const int64_t blocks = (int64_t)n * tiles_x * tiles_y;
-  IC2_CHECK_ARG(blocks < (1LL << 31), "from_rgb_conv_f16: too many tiles");
-  hipStream_t s = as_stream(stream);
-  if (cout_p == 32)
-    hipLaunchKernelGGL((from_rgb_kernel<32, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, cin, w, cout, bias,
-                       (bf16_t*)y, h, w_, tiles_x, tiles_y);
-  else if (cout_p == 64)
-    hipLaunchKernelGGL((from_rgb_kernel<64, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, cin, w, cout, bias,
-                       (bf16_t*)y, h, w_, tiles_x, tiles_y);
-  else
-    hipLaunchKernelGGL((from_rgb_kernel<128, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, cin, w, cout,
-                       bias, (bf16_t*)y, h, w_, tiles_x, tiles_y);
-  IC2_CHECK_LAUNCH("from_rgb_conv_f16");
-  return IC2_OK;
+  return launch_from_rgb<true, true>("from_rgb_conv_f16", x, cin, w, cout, bias, y, n, h, w_, cout_p, stream);
 }
 
 extern "C" int ic2_nhwc_to_nchw(const void* x, int dtype, float* y, int n, int c, int h, int w, int c_p, void* stream) {
@@ -789,18 +763,18 @@ extern "C" int64_t ic2_conv3x3_gn_stats_floats(int dtype, int n, int h, int w_, 
   return sep > fused ? sep : fused;
 }
 
-// VGGBlock conv (+ bias) and the GroupNorm statistics of its output.  When the halo
-// conv runs the layer, the per-tile (sum, sumsq) come out of its epilogue (no second read of y); otherwise the
-// separate two-stage statistics pass runs.  stats: ic2_conv3x3_gn_stats_floats() floats; the first n*groups*2 are
-// (mean, rstd) per (sample, group), as ic2_group_norm_stats writes them.
+// VGGBlock conv (+ bias) and the GroupNorm statistics of its output.  When an hg4
+// statistics-epilogue kernel runs the layer (the split modes; fuse: 0 = never, else the plan's choice), the per-tile
+// (sum, sumsq) come out of its epilogue (no second read of y); otherwise the separate two-stage statistics pass runs.
+// stats: ic2_conv3x3_gn_stats_floats() floats; the first n*groups*2 are (mean, rstd) per (sample, group), as
+// ic2_group_norm_stats writes them.
 static int conv3x3_gn_fwd_impl(const void* x, const void* w, void* y, int dtype, int n, int h, int w_, int cin_p,
                                int cout_p, int cout_valid, int kh, int kw, int pad, const float* bias, int groups,
                                float eps, float* stats, int64_t stats_floats, void* conv_ws, int64_t conv_ws_bytes,
-                               int fuse, void* stream, const float* in_gn, float in_slope, float out_mul = 1.f) {
+                               int fuse, void* stream, float out_mul = 1.f) {
   IC2_CHECK_ARG(x && w && y && stats && groups > 0 && cout_valid > 0 && cout_valid % groups == 0,
                 "conv3x3_gn_fwd: bad arguments");
-  // the encoder's precisions only: the fused statistics epilogue and the input-GroupNorm staging are bf16 halo-conv
-  // code, and an f16 operand must never reach the bf16 MFMA
+  // the encoder's inference precisions only (f16 activations go through ic2_conv_igemm_ws + ic2_group_norm_stats)
   IC2_CHECK_ARG(dtype == IC2_F32 || dtype == IC2_BF16 || dtype == IC2_BF16X3 || dtype == IC2_F16X2,
                 "conv3x3_gn_fwd: dtype must be IC2_F32, IC2_BF16, IC2_BF16X3 or IC2_F16X2");
   const int ho = h + 2 * pad - kh + 1, wo = w_ + 2 * pad - kw + 1;
@@ -810,8 +784,7 @@ static int conv3x3_gn_fwd_impl(const void* x, const void* w, void* y, int dtype,
   const int64_t sf = ((int64_t)n * groups * 2 + 1) / 2 * 2;
   double* part = reinterpret_cast<double*>(stats + sf);
   const int nch = conv_gn_fused(x, w, y, dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, bias, groups, part,
-                                (stats_floats - sf) / 2, conv_ws, conv_ws_bytes, fuse, s, in_gn, in_slope, out_mul);
-  if (nch == -2) return IC2_E_UNSUPPORTED;
+                                (stats_floats - sf) / 2, conv_ws, conv_ws_bytes, fuse, s, out_mul);
   if (nch < 0) return IC2_E_INVALID;
   if (nch == 0)  // split inputs: the conv wrote f32 (split bf16) / f16 (split-weight f16)
     return ic2_group_norm_stats(y, dtype == IC2_BF16X3 ? IC2_F32 : dtype == IC2_F16X2 ? IC2_F16 : dtype, n, ho * wo, cout_p, cout_valid, groups, eps,
@@ -832,7 +805,7 @@ extern "C" int ic2_conv3x3_gn_fwd(const void* x, const void* w, void* y, int dty
                                   float eps, float* stats, int64_t stats_floats, void* conv_ws, int64_t conv_ws_bytes,
                                   int fuse, void* stream) {
   return conv3x3_gn_fwd_impl(x, w, y, dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, bias, groups, eps, stats,
-                             stats_floats, conv_ws, conv_ws_bytes, fuse, stream, nullptr, 0.f);
+                             stats_floats, conv_ws, conv_ws_bytes, fuse, stream);
 }
 
 extern "C" int ic2_conv3x3_gn_fwd_scaled(const void* x, const void* w, void* y, int dtype, int n, int h, int w_,
@@ -842,52 +815,7 @@ extern "C" int ic2_conv3x3_gn_fwd_scaled(const void* x, const void* w, void* y, 
                                          void* stream) {
   IC2_CHECK_ARG(dtype == IC2_F16X2 && out_mul > 0.f, "conv3x3_gn_fwd_scaled: IC2_F16X2 with out_mul > 0 only");
   return conv3x3_gn_fwd_impl(x, w, y, dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, bias, groups, eps, stats,
-                             stats_floats, conv_ws, conv_ws_bytes, fuse, stream, nullptr, 0.f, out_mul);
-}
-
-// (mean, rstd * gamma, beta, 0) per (sample, channel) from GroupNorm stats [n][groups][2] (mean, rstd): the operands
-// of gn_apply_oct_kernel, for a consumer that applies GroupNorm + lrelu while it loads (padded channels: 0)
-__global__ void __launch_bounds__(256) gn_affine_table_kernel(const float* __restrict__ stats,
-                                                              const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, int n, int c, int c_p,
-                                                              int groups, float4* __restrict__ table) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= n * c_p) return;
-  const int ch = e % c_p, nn = e / c_p;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ch < c) {
-    const int g = ch / (c / groups);
-    v.x = stats[((int64_t)nn * groups + g) * 2 + 0];
-    v.y = stats[((int64_t)nn * groups + g) * 2 + 1] * gamma[ch];
-    v.z = beta[ch];
-  }
-  table[e] = v;
-}
-
-extern "C" int ic2_gn_affine_table(const float* stats, const float* gamma, const float* beta, int n, int c, int c_p,
-                                   int groups, float* table, void* stream) {
-  IC2_CHECK_ARG(stats && gamma && beta && table && n > 0 && c > 0 && c <= c_p && groups > 0 && c % groups == 0,
-                "gn_affine_table: bad arguments");
-  IC2_CHECK_ARG((uintptr_t)table % 16 == 0, "gn_affine_table: table must be 16-byte aligned");
-  hipLaunchKernelGGL(gn_affine_table_kernel, dim3((unsigned)ceil_div((int64_t)n * c_p, 256)), dim3(256), 0,
-                     as_stream(stream), stats, gamma, beta, n, c, c_p, groups, reinterpret_cast<float4*>(table));
-  IC2_CHECK_LAUNCH("gn_affine_table");
-  return IC2_OK;
-}
-
-extern "C" int ic2_conv3x3_gnin_supported(int dtype, int n, int h, int w_, int cin_p, int cout_p, int kh, int kw,
-                                          int pad) {
-  return conv_gn_in_supported(dtype, n, h, w_, cin_p, cout_p, kh, kw, pad) ? 1 : 0;
-}
-
-extern "C" int ic2_conv3x3_gnin_gn_fwd(const void* x, const float* in_gn, float in_slope, const void* w, void* y,
-                                       int dtype, int n, int h, int w_, int cin_p, int cout_p, int cout_valid, int kh,
-                                       int kw, int pad, const float* bias, int groups, float eps, float* stats,
-                                       int64_t stats_floats, void* conv_ws, int64_t conv_ws_bytes, int fuse,
-                                       void* stream) {
-  IC2_CHECK_ARG(in_gn != nullptr && (uintptr_t)in_gn % 16 == 0, "conv3x3_gnin_gn_fwd: in_gn must be a 16-byte aligned table");
-  return conv3x3_gn_fwd_impl(x, w, y, dtype, n, h, w_, cin_p, cout_p, cout_valid, kh, kw, pad, bias, groups, eps, stats,
-                             stats_floats, conv_ws, conv_ws_bytes, fuse, stream, in_gn, in_slope);
+                             stats_floats, conv_ws, conv_ws_bytes, fuse, stream, out_mul);
 }
 
 extern "C" int ic2_gn_lrelu_pool(const void* y, void* out, int dtype_in, int dtype_out, int n, int h, int w, int c_p,

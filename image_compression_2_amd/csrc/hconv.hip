@@ -13,23 +13,6 @@
 
 namespace ic2 {
 
-// lrelu((v - mean) * scale + shift) on 8 bf16 values, rounded back to bf16: the arithmetic of
-// gn_apply_oct_kernel (encoder_ops.hip) on the same operands, so a fused input equals the materialised one bit for bit
-__device__ __forceinline__ uint4 gn_lrelu_bf16x8(uint4 u, const float4 (&p)[8], float slope) {
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-  uint32_t o[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    float lo = __uint_as_float(w[k] << 16), hi = __uint_as_float(w[k] & 0xffff0000u);
-    lo = __builtin_fmaf(lo - p[2 * k].x, p[2 * k].y, p[2 * k].z);
-    hi = __builtin_fmaf(hi - p[2 * k + 1].x, p[2 * k + 1].y, p[2 * k + 1].z);
-    lo = lo < 0.f ? lo * slope : lo;
-    hi = hi < 0.f ? hi * slope : hi;
-    o[k] = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
-  }
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
 template <int CINP, int COUTP, int TH>
 struct HcCfg {
   static constexpr int TW = 32, HR = TH + 2, HC = TW + 2;
@@ -41,10 +24,9 @@ struct HcCfg {
   static constexpr int PER_T = (NPIECE + 511) / 512;
 };
 
-template <int CINP, int COUTP, int TH, bool GN, bool F16 = false>
+template <int CINP, int COUTP, int TH, bool F16 = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(CINP == 32 ? 4 : 1)))
 hconv_kernel(IgemmArgs a, int tiles_x, int tiles_y, int ntiles) {
-  static_assert(!(F16 && GN), "the fused GroupNorm statistics are an encoder (bf16) feature");
   using C = HcCfg<CINP, COUTP, TH>;
   __shared__ __attribute__((aligned(16))) char lds[C::HALO_B + C::W_B];
   char* const halo = lds;
@@ -65,19 +47,12 @@ hconv_kernel(IgemmArgs a, int tiles_x, int tiles_y, int ntiles) {
 
   const char* xg = reinterpret_cast<const char*>(a.x);
   uint4 pre[C::PER_T];
-  // input GroupNorm + lrelu (a.in_gn; the 64-channel instances only -- the 32-channel ones run at 4 waves per SIMD
-  // and would spill the 32 extra VGPRs): 512 % 8 == 0, so a thread's pieces all hold channels (tid % 8) * 8 .. +7,
-  // whose (mean, scale, shift) are loaded once per tile
-  constexpr bool kGnIn = CINP == 64;
-  float4 gnp[8];
-  uint32_t inimg = 0;
   auto fetch = [&](int t) {
     const int tx = t % tiles_x;
     const int t2 = t / tiles_x;
     const int ty = t2 % tiles_y;
     const int nn = t2 / tiles_y;
     const int y0 = ty * TH - a.pad, x0 = tx * C::TW - a.pad;
-    inimg = 0;
 #pragma unroll
     for (int k = 0; k < C::PER_T; ++k) {
       const int e = tid + 512 * k;
@@ -85,16 +60,8 @@ hconv_kernel(IgemmArgs a, int tiles_x, int tiles_y, int ntiles) {
       const int hr = pi / C::HC, hc = pi - hr * C::HC;
       const int iy = y0 + hr, ix = x0 + hc;
       const bool ok = e < C::NPIECE && (unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w_;
-      inimg |= (uint32_t)ok << k;
       pre[k] = ok ? *reinterpret_cast<const uint4*>(xg + ((((int64_t)nn * a.h + iy) * a.w_ + ix) * CINP + part * 8) * 2)
                   : make_uint4(0u, 0u, 0u, 0u);
-    }
-    if constexpr (kGnIn) {
-      if (a.in_gn) {
-        const float4* tb = reinterpret_cast<const float4*>(a.in_gn) + ((int64_t)nn * CINP + (tid % (CINP / 8)) * 8);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) gnp[c] = tb[c];
-      }
     }
   };
   if (blockIdx.x < ntiles) fetch(blockIdx.x);
@@ -106,11 +73,7 @@ hconv_kernel(IgemmArgs a, int tiles_x, int tiles_y, int ntiles) {
       const int e = tid + 512 * k;
       if (e < C::NPIECE) {
         const int pi = e / (CINP / 8), part = e - pi * (CINP / 8);
-        uint4 v = pre[k];
-        if constexpr (kGnIn) {  // zero padding stays zero: only in-image pieces are normalised
-          if (a.in_gn && ((inimg >> k) & 1u)) v = gn_lrelu_bf16x8(v, gnp, a.in_slope);
-        }
-        *reinterpret_cast<uint4*>(halo + pi * C::PPB + part * 16) = v;
+        *reinterpret_cast<uint4*>(halo + pi * C::PPB + part * 16) = pre[k];
       }
     }
     __syncthreads();
@@ -149,16 +112,6 @@ hconv_kernel(IgemmArgs a, int tiles_x, int tiles_y, int ntiles) {
     const int t2 = t / tiles_x;
     const int ty = t2 % tiles_y;
     const int nn = t2 / tiles_y;
-    // GN (fused statistics, groups = 32 over all COUTP channels): CPG = COUTP / 32 channels per group, so a
-    // lane's 4 channels 16i + 4fh .. +3 fall in 4 / CPG groups
-    constexpr int CPG = COUTP / 32, GL = 4 / CPG;
-    float gs[C::OB][GL], gq[C::OB][GL];
-    if constexpr (GN) {
-#pragma unroll
-      for (int i = 0; i < C::OB; ++i)
-#pragma unroll
-        for (int r = 0; r < GL; ++r) gs[i][r] = gq[i][r] = 0.f;
-    }
     // every channel block's operands before the first store (see ig_load_oscale); not in the 32 -> 64 instance,
     // whose 4-waves-per-SIMD register budget (128) would spill them (measured 142 -> 179 us on e0a) and whose
     // occupancy hides the per-block loads instead
@@ -187,59 +140,12 @@ hconv_kernel(IgemmArgs a, int tiles_x, int tiles_y, int ntiles) {
           bi[i] = ig_load_bias(a, 16 * i + 4 * fh);
         }
         ig_store4v(a, p, nn, pix, 16 * i + 4 * fh, v, sc[i], bi[i]);
-        if constexpr (GN) {  // statistics of the value as stored: bias added, rounded to bf16
-          const float bv[4] = {bi[i].x, bi[i].y, bi[i].z, bi[i].w};
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float st = bf2f(f2bf(v[r] + bv[r]));
-            gs[i][r / CPG] += st;
-            gq[i][r / CPG] += st * st;
-          }
-        }
       }
-    }
-    if constexpr (GN) {
-      // wave: sum over the 16 pixel lanes; workgroup: 8 waves through LDS (the halo region, after a barrier);
-      // then one thread per group sums the waves in a fixed order -> part[(nn, g, tile)]
-#pragma unroll
-      for (int i = 0; i < C::OB; ++i)
-#pragma unroll
-        for (int r = 0; r < GL; ++r)
-#pragma unroll
-          for (int off = 1; off < 16; off <<= 1) {
-            gs[i][r] += __shfl_xor(gs[i][r], off, 64);
-            gq[i][r] += __shfl_xor(gq[i][r], off, 64);
-          }
-      __syncthreads();  // every wave is past its halo reads
-      float* red = reinterpret_cast<float*>(halo);  // [2][8 waves][32 groups]
-      if (fr == 0) {
-#pragma unroll
-        for (int i = 0; i < C::OB; ++i)
-#pragma unroll
-          for (int r = 0; r < GL; ++r) {
-            const int g = (16 * i + 4 * fh) / CPG + r;
-            red[wave * 32 + g] = gs[i][r];
-            red[(8 + wave) * 32 + g] = gq[i][r];
-          }
-      }
-      __syncthreads();
-      if (tid < 32) {
-        double sg = 0.0, qg = 0.0;
-#pragma unroll
-        for (int w8 = 0; w8 < 8; ++w8) {
-          sg += (double)red[w8 * 32 + tid];
-          qg += (double)red[(8 + w8) * 32 + tid];
-        }
-        double* o = a.gn_part + (((int64_t)nn * 32 + tid) * (tiles_x * tiles_y) + (ty * tiles_x + tx)) * 2;
-        o[0] = sg;
-        o[1] = qg;
-      }
-      // the next tile's first barrier orders these LDS reads before its halo stores
     }
   }
 }
 
-template <int CINP, int COUTP, bool GN, bool F16>
+template <int CINP, int COUTP, bool F16>
 static void launch_hconv_t(const IgemmArgs& a, hipStream_t s) {
   constexpr int TH = CINP > 64 ? 4 : 8;  // 96 channels: 4-row tiles keep halo + weight within 160 KB of LDS
   const int tiles_x = (int)ceil_div(a.wo, 32), tiles_y = (int)ceil_div(a.ho, TH);
@@ -249,28 +155,26 @@ static void launch_hconv_t(const IgemmArgs& a, hipStream_t s) {
     int dev = 0, cus = 0, per_cu = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hconv_kernel<CINP, COUTP, TH, GN, F16>, 512, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hconv_kernel<CINP, COUTP, TH, F16>, 512, 0);
     resident = (cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 1);
   }
   const int grid = ntiles < resident ? ntiles : resident;
-  hipLaunchKernelGGL((hconv_kernel<CINP, COUTP, TH, GN, F16>), dim3((unsigned)grid), dim3(512), 0, s, a, tiles_x,
+  hipLaunchKernelGGL((hconv_kernel<CINP, COUTP, TH, F16>), dim3((unsigned)grid), dim3(512), 0, s, a, tiles_x,
                      tiles_y, ntiles);
 }
 // the instance of a's cin_p in {32, 64, 96} x cout_p in {32, 64} (hconv_eligible, conv_dispatch.hip)
-template <bool GN, bool F16>
+template <bool F16>
 static void launch_hconv_cfg(const IgemmArgs& a, hipStream_t s) {
-  if (a.cin_p == 32 && a.cout_p == 32) launch_hconv_t<32, 32, GN, F16>(a, s);
-  else if (a.cin_p == 32) launch_hconv_t<32, 64, GN, F16>(a, s);
-  else if (a.cin_p == 64 && a.cout_p == 32) launch_hconv_t<64, 32, GN, F16>(a, s);
-  else if (a.cin_p == 64) launch_hconv_t<64, 64, GN, F16>(a, s);
-  else if (a.cout_p == 32) launch_hconv_t<96, 32, GN, F16>(a, s);
-  else launch_hconv_t<96, 64, GN, F16>(a, s);
+  if (a.cin_p == 32 && a.cout_p == 32) launch_hconv_t<32, 32, F16>(a, s);
+  else if (a.cin_p == 32) launch_hconv_t<32, 64, F16>(a, s);
+  else if (a.cin_p == 64 && a.cout_p == 32) launch_hconv_t<64, 32, F16>(a, s);
+  else if (a.cin_p == 64) launch_hconv_t<64, 64, F16>(a, s);
+  else if (a.cout_p == 32) launch_hconv_t<96, 32, F16>(a, s);
+  else launch_hconv_t<96, 64, F16>(a, s);
 }
-// gn_stats: the fused GroupNorm statistics (a.gn_part), bf16 only
-void launch_hconv(const IgemmArgs& a, bool gn_stats, bool f16, hipStream_t s) {
-  if (gn_stats) launch_hconv_cfg<true, false>(a, s);
-  else if (f16) launch_hconv_cfg<false, true>(a, s);
-  else launch_hconv_cfg<false, false>(a, s);
+void launch_hconv(const IgemmArgs& a, bool f16, hipStream_t s) {
+  if (f16) launch_hconv_cfg<true>(a, s);
+  else launch_hconv_cfg<false>(a, s);
 }
 
 // ------------------------------------------------------------------------------------------------

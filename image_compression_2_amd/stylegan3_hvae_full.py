@@ -119,18 +119,12 @@ def _conv(conv: nn.Conv2d, x: _Act, dt, cache: dict, stream):
     return _Act(y, cout)
 
 
-# knob IC2_FROM_RGB_DIRECT=0 (IC2_DEV=1) keeps the packing + implicit-GEMM from_rgb (A/B switch)
-_FROM_RGB_DIRECT = nv.knob("IC2_FROM_RGB_DIRECT", 1) != 0
-# knob IC2_SPLIT_F16_BLOCKS: in the split ('bf16x3') mode the first K blocks' convs take f16 activations against
-# split f16 weights (IC2_F16X2, two f16 MFMAs per product instead of three bf16 ones): K = 3 (blocks 0-2,
-# the 1024^2 .. 256^2 levels at C4) by default, 0 = every conv split bf16.  Measured (profiles/r5_split_f16_blocks.txt):
-# K 0 / 2 / 3 -> C4 316 / 340 / 346 img/s, C2 1426 / 1451 / 1461 (f32 conv outputs), C2 index mismatches 18 / 37 / 34
-# of 262144; with f16 conv outputs (default) K = 3 -> C4 371-378, C2 1482-1520, 63 mismatches
-_SPLIT_F16_BLOCKS = nv.knob("IC2_SPLIT_F16_BLOCKS", 3)
-# knob IC2_GN_IN_FUSE=1 applies norm1 + lrelu inside conv2's halo-conv staging instead of materialising it.  Bit-identical
-# but measured level on MI355X (C2 1438.0 -> 1439.4, C4 415.5 -> 415.9 img/s, same box: the saved pass is paid back in
-# the heavier staging of the 64-channel halo conv), so off by default
-_GN_IN_FUSE = nv.knob("IC2_GN_IN_FUSE", 0) == 1
+# In the split ('bf16x3') mode the convs of the first K encoder blocks take f16 activations against split f16 weights
+# (IC2_F16X2, two f16 MFMAs per product instead of three bf16 ones): K = 3 (blocks 0-2, the 1024^2 ..
+# 256^2 levels at C4); K = 0 would be every conv split bf16.  Measured (profiles/r5_split_f16_blocks.txt): K 0 / 2 / 3
+# -> C4 316 / 340 / 346 img/s, C2 1426 / 1451 / 1461 (f32 conv outputs), C2 index mismatches 18 / 37 / 34 of 262144;
+# with f16 conv outputs (what runs) K = 3 -> C4 371-378, C2 1482-1520, 63 mismatches
+_SPLIT_F16_BLOCKS = 3
 
 
 def _from_rgb(conv: nn.Conv2d, x, dt, cache: dict, stream, split=False, h2=False):
@@ -171,7 +165,7 @@ def _from_rgb(conv: nn.Conv2d, x, dt, cache: dict, stream, split=False, h2=False
             nv.call("ic2_nchw_to_nhwc", nv.ptr(yf), nv.ptr(y), nv.BF16X3, n, cout, ho, wo, cout_p, None, stream)
         return _Act(y, cout, x3=True)
     if (dt == torch.bfloat16 and cin <= 4 and kh == 3 and kw == 3 and conv.padding[0] == 1
-            and nv.pad32(cout) in (32, 64) and _FROM_RGB_DIRECT):
+            and nv.pad32(cout) in (32, 64)):
         n, _, hh, ww = x.shape
         fake = types.SimpleNamespace(c=cin, c_p=nv.pad32(cin))
         wp, bp = _packed(conv, fake, dt, cache, stream)
@@ -183,10 +177,19 @@ def _from_rgb(conv: nn.Conv2d, x, dt, cache: dict, stream, split=False, h2=False
     return _conv(conv, _to_nhwc(x, dt, stream), dt, cache, stream)
 
 
-def _conv_gn(conv: nn.Conv2d, norm: nn.GroupNorm, x: _Act, dt, cache: dict, stream, fuse=-1, in_gn=None):
-    """conv (+ bias) and the GroupNorm statistics of its output in one call (ic2_conv3x3_gn_fwd: fused into the
-    halo conv's epilogue where that kernel runs the layer).  in_gn = (affine table, slope): the previous GroupNorm +
-    lrelu applied to x while the halo conv stages it (ic2_conv3x3_gnin_gn_fwd).  -> (y, stats)."""
+def _gn_stats(norm: nn.GroupNorm, y: _Act, stream):
+    """The GroupNorm (mean, rstd) of y by the separate two-stage pass (ic2_group_norm_stats) -> stats buffer."""
+    nfl = int(nv.query("ic2_group_norm_stats_floats", y.n, y.h * y.w, norm.num_groups))
+    stats = torch.empty([nfl], dtype=torch.float32, device=y.t.device)
+    nv.call("ic2_group_norm_stats", nv.ptr(y.t), nv.dtype_code(y.t.dtype), y.n, y.h * y.w, y.c_p, y.c, norm.num_groups,
+            float(norm.eps), nv.ptr(stats), stream)
+    return stats
+
+
+def _conv_gn(conv: nn.Conv2d, norm: nn.GroupNorm, x: _Act, dt, cache: dict, stream, fuse=-1):
+    """conv (+ bias) and the GroupNorm statistics of its output (ic2_conv3x3_gn_fwd: out of the conv's epilogue where
+    an hg4 statistics kernel runs the layer, the split modes' 64- / 128-wide ones; fuse=0 refuses that).
+    -> (y, stats)."""
     cout, cin, kh, kw = conv.weight.shape
     pad = conv.padding[0]
     wp, bp = _packed(conv, x, dt, cache, stream)
@@ -221,20 +224,12 @@ def _conv_gn(conv: nn.Conv2d, norm: nn.GroupNorm, x: _Act, dt, cache: dict, stre
                       cout, kh, kw, pad, ho, wo, None, nv.ptr(bp), 0, 0.0, 1.0, -1.0, _out_mul(conv, cache), nv.NHWC,
                       stream, x.t.device)
         ya = _Act(y, cout)
-        nfl = int(nv.query("ic2_group_norm_stats_floats", ya.n, ya.h * ya.w, norm.num_groups))
-        stats = torch.empty([nfl], dtype=torch.float32, device=y.device)
-        nv.call("ic2_group_norm_stats", nv.ptr(y), nv.dtype_code(ydt), ya.n, ya.h * ya.w, ya.c_p, ya.c,
-                norm.num_groups, float(norm.eps), nv.ptr(stats), stream)
-        return ya, stats
+        return ya, _gn_stats(norm, ya, stream)
     if dt == torch.float16:
-        # f16 (the training precision's inference forward): the conv, then the separate statistics pass (the fused
-        # statistics epilogue is bf16 halo-conv code)
+        # f16 (the training precision's inference forward): the conv, then the separate statistics pass
+        # (ic2_conv3x3_gn_fwd takes no f16 operands)
         ya = _conv(conv, x, dt, cache, stream)
-        nfl = int(nv.query("ic2_group_norm_stats_floats", ya.n, ya.h * ya.w, norm.num_groups))
-        stats = torch.empty([nfl], dtype=torch.float32, device=ya.t.device)
-        nv.call("ic2_group_norm_stats", nv.ptr(ya.t), nv.F16, ya.n, ya.h * ya.w, ya.c_p, ya.c, norm.num_groups,
-                float(norm.eps), nv.ptr(stats), stream)
-        return ya, stats
+        return ya, _gn_stats(norm, ya, stream)
     dc = nv.dtype_code(dt)
     y = torch.empty([x.n, ho, wo, cout_p], dtype=dt, device=x.t.device)
     nfl = int(nv.query("ic2_conv3x3_gn_stats_floats", dc, x.n, x.h, x.w, x.c_p, cout_p, kh, kw, pad, norm.num_groups))
@@ -242,30 +237,10 @@ def _conv_gn(conv: nn.Conv2d, norm: nn.GroupNorm, x: _Act, dt, cache: dict, stre
     nbytes = int(nv.query("ic2_conv_igemm_ws_bytes", dc, x.n, x.h, x.w, x.c_p, cout_p, kh, kw, pad))
     ws = torch.empty([max(nbytes, 16) // 4], dtype=torch.float32, device=x.t.device) if nbytes > 0 else None
     nv.note_flops(_conv_flops(x.n, ho, wo, cout, cin, kh, kw))
-    if in_gn is not None:
-        nv.call("ic2_conv3x3_gnin_gn_fwd", nv.ptr(x.t), nv.ptr(in_gn[0]), float(in_gn[1]), nv.ptr(wp), nv.ptr(y), dc,
-                x.n, x.h, x.w, x.c_p, cout_p, cout, kh, kw, pad, nv.ptr(bp), norm.num_groups, float(norm.eps),
-                nv.ptr(stats), nfl, nv.ptr(ws), nbytes, int(fuse), stream)
-    else:
-        nv.call("ic2_conv3x3_gn_fwd", nv.ptr(x.t), nv.ptr(wp), nv.ptr(y), dc, x.n, x.h, x.w, x.c_p, cout_p, cout, kh,
-                kw, pad, nv.ptr(bp), norm.num_groups, float(norm.eps), nv.ptr(stats), nfl, nv.ptr(ws), nbytes,
-                int(fuse), stream)
+    nv.call("ic2_conv3x3_gn_fwd", nv.ptr(x.t), nv.ptr(wp), nv.ptr(y), dc, x.n, x.h, x.w, x.c_p, cout_p, cout, kh,
+            kw, pad, nv.ptr(bp), norm.num_groups, float(norm.eps), nv.ptr(stats), nfl, nv.ptr(ws), nbytes,
+            int(fuse), stream)
     return _Act(y, cout), stats
-
-
-def _gn_in_fusable(conv: nn.Conv2d, y: _Act, dt):
-    """Can conv consume lrelu(GroupNorm(y)) through ic2_conv3x3_gnin_gn_fwd (the halo conv runs the shape)?"""
-    cout, cin, kh, kw = conv.weight.shape
-    return (_GN_IN_FUSE and dt == torch.bfloat16 and y.t.dtype == torch.bfloat16 and
-            bool(nv.query("ic2_conv3x3_gnin_supported", nv.BF16, y.n, y.h, y.w, y.c_p, nv.pad32(cout), kh, kw,
-                          conv.padding[0])))
-
-
-def _gn_affine_table(norm: nn.GroupNorm, y: _Act, stats, stream):
-    table = torch.empty([y.n, y.c_p, 4], dtype=torch.float32, device=y.t.device)
-    nv.call("ic2_gn_affine_table", nv.ptr(stats), nv.ptr(norm.weight), nv.ptr(norm.bias), y.n, y.c, y.c_p,
-            norm.num_groups, nv.ptr(table), stream)
-    return table
 
 
 def _group_norm_lrelu(norm: nn.GroupNorm, y: _Act, pool: bool, dt, stream, slope=0.2, stats=None, split=False,
@@ -275,10 +250,7 @@ def _group_norm_lrelu(norm: nn.GroupNorm, y: _Act, pool: bool, dt, stream, slope
     f16 instead (the operand of a split-weight f16 conv)."""
     groups = norm.num_groups
     if stats is None:
-        nfl = int(nv.query("ic2_group_norm_stats_floats", y.n, y.h * y.w, groups))
-        stats = torch.empty([nfl], dtype=torch.float32, device=y.t.device)
-        nv.call("ic2_group_norm_stats", nv.ptr(y.t), nv.dtype_code(y.t.dtype), y.n, y.h * y.w, y.c_p, y.c, groups,
-                float(norm.eps), nv.ptr(stats), stream)
+        stats = _gn_stats(norm, y, stream)
     oh, ow = (y.h // 2, y.w // 2) if pool else (y.h, y.w)
     if split and h2:
         out = torch.empty([y.n, oh, ow, y.c_p], dtype=torch.float16, device=y.t.device)
@@ -482,13 +454,8 @@ class VGGBlock(nn.Module):
         weights, h2_next = so does the next block's conv1 (the pooled output stored f16); else split bf16."""
         split = x.split
         y, st = _conv_gn(self.conv1, self.norm1, x, dt, cache, stream)
-        if not split and _gn_in_fusable(self.conv2, y, dt):
-            # norm1 + lrelu applied while conv2's halo conv stages its input: lrelu(norm1(y)) never reaches HBM
-            y, st = _conv_gn(self.conv2, self.norm2, y, dt, cache, stream,
-                             in_gn=(_gn_affine_table(self.norm1, y, st, stream), 0.2))
-        else:
-            h = _group_norm_lrelu(self.norm1, y, False, dt, stream, stats=st, split=split, h2=h2)
-            y, st = _conv_gn(self.conv2, self.norm2, h, dt, cache, stream)
+        h = _group_norm_lrelu(self.norm1, y, False, dt, stream, stats=st, split=split, h2=h2)
+        y, st = _conv_gn(self.conv2, self.norm2, h, dt, cache, stream)
         pool = y.h > 1 and y.w > 1
         return _group_norm_lrelu(self.norm2, y, pool, dt, stream, stats=st, split=split, h2=h2_next)
 

@@ -412,13 +412,12 @@ int ic2_gap_bwd(const float* dpooled, void* dx, int dtype, int n, int hw, int c_
 
 /* VGGBlock conv + GroupNorm statistics (SURVEY 8b `ic2_conv3x3_gn_fwd`; stylegan3_hvae_full.py:175-191, the
  * conv1/conv2 -> norm1/norm2 pairs): y = conv(x, w) + bias (NHWC, dtype = the activation dtype) and the GroupNorm
- * (mean, rstd) per (sample, group) of y's first cout_valid channels in stats[0 .. 2*n*groups).  When the halo conv
- * kernel runs the layer (bf16, cin_p <= 96, cout_p <= 64) the per-tile sums come out of its epilogue, computed on the
- * stored (rounded) values, so y is not read a second time; otherwise the two-stage statistics pass of
- * ic2_group_norm_stats runs after the conv.  stats: ic2_conv3x3_gn_stats_floats() floats (statistics + partial
- * sums); conv_ws / conv_ws_bytes: the conv's split-K workspace as for ic2_conv_igemm_ws.  fuse: 1 = fused statistics
- * where the halo conv runs, 0 = always the separate pass, -1 = default (separate: the fusion measured at parity on
- * MI355X).  Deterministic.  dtype IC2_BF16X3: the split-bf16 encoder -- x stored
+ * (mean, rstd) per (sample, group) of y's first cout_valid channels in stats[0 .. 2*n*groups).  For IC2_F32 and
+ * IC2_BF16 the conv runs as ic2_conv_igemm_ws does and the two-stage statistics pass of ic2_group_norm_stats after it.
+ * stats: ic2_conv3x3_gn_stats_floats() floats (statistics + partial sums); conv_ws / conv_ws_bytes: the conv's
+ * split-K workspace as for ic2_conv_igemm_ws.  fuse: 0 = always the separate statistics pass, any other value = the
+ * plan's choice (only the split modes below have a kernel that carries the statistics; the bf16 halo conv's
+ * statistics epilogue measured a loss and was removed).  Deterministic.  dtype IC2_BF16X3: x stored
  * [hi | lo] with cin_p = the tripled (GEMM K) channel count, w from ic2_pack_weight(IC2_BF16X3), y f32 NHWC; the
  * statistics come out of the 4-wave halo GEMM's epilogue (on the f32 values as stored) when it runs a 64- / 128-wide
  * layer with 32 groups (fuse != 0), else the separate pass.  dtype IC2_F16X2: the same with the f16 input and
@@ -439,20 +438,6 @@ int ic2_conv3x3_gn_fwd_scaled(const void* x, const void* w, void* y, int dtype, 
 /* 1 when ic2_conv3x3_gn_fwd with these arguments takes the statistics from the conv's epilogue (a host query). */
 int ic2_conv3x3_gn_fuses(int dtype, int n, int h, int w, int cin_p, int cout_p, int cout_valid, int kh, int kw, int pad,
                          int groups, int fuse);
-
-/* VGGBlock's second conv with the first GroupNorm + lrelu applied to its INPUT as the halo conv stages it
- * (stylegan3_hvae_full.py:183-191: conv2(lrelu(norm1(conv1(x))))): the normalised activation is never written to
- * HBM.  x = conv1's raw output (bf16 NHWC, cin_p 64); in_gn = ic2_gn_affine_table() of norm1 [n][cin_p][4] f32;
- * in_slope = the lrelu slope; zero padding stays zero (the reference pads the normalised activation).  Otherwise as
- * ic2_conv3x3_gn_fwd.  Bit-identical to ic2_gn_lrelu_pool (no pool) followed by ic2_conv3x3_gn_fwd.  Returns
- * IC2_E_UNSUPPORTED unless ic2_conv3x3_gnin_supported() (the halo conv runs the shape). */
-int ic2_conv3x3_gnin_supported(int dtype, int n, int h, int w, int cin_p, int cout_p, int kh, int kw, int pad);
-int ic2_gn_affine_table(const float* stats, const float* gamma, const float* beta, int n, int c, int c_p, int groups,
-                        float* table, void* stream);
-int ic2_conv3x3_gnin_gn_fwd(const void* x, const float* in_gn, float in_slope, const void* w, void* y, int dtype, int n,
-                            int h, int w_, int cin_p, int cout_p, int cout_valid, int kh, int kw, int pad,
-                            const float* bias, int groups, float eps, float* stats, int64_t stats_floats, void* conv_ws,
-                            int64_t conv_ws_bytes, int fuse, void* stream);
 
 /* Backward of ic2_flrelu_nhwc w.r.t. its input (SynthesisLayer's filtered_lrelu, SG3-public; the encoder's loss
  * reaches W+ through it, :669-696): x = the forward's input (NHWC [n][in_h][in_w][c_p], f32 or f16), gout = the

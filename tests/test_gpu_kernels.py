@@ -507,38 +507,6 @@ def test_conv_split_384(cuda, cin, cout, size, pad, dtype):
     _conv_case(cin, cout, size, pad, dtype, n=8)
 
 
-@pytest.mark.parametrize("cin,h,w", [(32, 130, 131), (64, 129, 130)])
-def test_vggblock_gn_input_fusion_bit_identical(cuda, cin, h, w):
-    """VGGBlock.run_nhwc in bf16 with norm1 + lrelu fused into conv2's halo-conv input staging
-    (ic2_conv3x3_gnin_gn_fwd) gives the same bits as the materialised lrelu(norm1(conv1)) path (ragged tiles and
-    the zero padding of the normalised activation included), and the fused path is the one that ran."""
-    from image_compression_2_amd import stylegan3_hvae_full as shf
-    g = torch.Generator().manual_seed(cin + h)
-    torch.manual_seed(cin + h)
-    blk = shf.VGGBlock(cin, 64).to(cuda)
-    with torch.no_grad():
-        for nrm in (blk.norm1, blk.norm2):
-            nrm.weight.copy_(torch.rand(64, generator=g) + 0.5)
-            nrm.bias.copy_(torch.randn(64, generator=g) * 0.3)
-    n = 4
-    x = (torch.randn(n, h, w, cin, generator=g) * 2).to(torch.bfloat16).to(cuda)
-    xa = shf._Act(x, cin)
-    stream = nv.stream_of(x)
-    y1, _ = shf._conv_gn(blk.conv1, blk.norm1, xa, torch.bfloat16, {}, stream)
-    saved = shf._GN_IN_FUSE
-    outs = []
-    try:
-        for fuse in (True, False):
-            shf._GN_IN_FUSE = fuse
-            assert shf._gn_in_fusable(blk.conv2, y1, torch.bfloat16) == fuse
-            with torch.no_grad():
-                outs.append(blk.run_nhwc(xa, torch.bfloat16, {}, stream).t.clone())
-    finally:
-        shf._GN_IN_FUSE = saved
-    torch.cuda.synchronize()
-    assert torch.equal(outs[0], outs[1])
-
-
 @pytest.mark.parametrize("cin,cout,n,h,w", [(3, 32, 3, 67, 45), (3, 64, 2, 40, 33), (1, 32, 1, 9, 70), (4, 32, 2, 16, 32)])
 def test_from_rgb_direct(cuda, cin, cout, n, h, w):
     """ic2_from_rgb_conv (from_rgb read straight from the NCHW f32 image, bf16 NHWC out) against F.conv2d in fp64
@@ -653,11 +621,11 @@ def test_group_norm_lrelu_pool_matches_torch(cuda, n, c, groups, h, w, pool, dty
 @pytest.mark.parametrize("cin,cout,n,h,w", [(32, 64, 2, 200, 181), (64, 64, 1, 257, 263), (3, 32, 2, 190, 200),
                                              (64, 32, 2, 181, 190), (96, 64, 1, 300, 230), (128, 128, 2, 64, 70),
                                              (32, 64, 1, 16, 20)])
-@pytest.mark.parametrize("fuse", [1, 0])
+@pytest.mark.parametrize("fuse", [0])
 def test_conv3x3_gn_fwd_statistics(cuda, cin, cout, n, h, w, fuse):
-    """ic2_conv3x3_gn_fwd: the conv output is the plain conv's, and the GroupNorm statistics -- fused
-    into the halo conv's epilogue for the bf16 <= 96 -> <= 64 channel layers (edge tiles included), the separate
-    pass otherwise -- match ic2_group_norm_stats on the same stored output (fp64 partial sums, 1e-5 relative)."""
+    """ic2_conv3x3_gn_fwd in bf16: the conv output is the plain conv's, and the GroupNorm statistics (the
+    separate pass; the halo conv's statistics epilogue, fuse=1, is gone) match ic2_group_norm_stats on the same stored
+    output (fp64 partial sums, 1e-5 relative)."""
     from image_compression_2_amd.stylegan3_hvae_full import _conv_gn
     g = torch.Generator().manual_seed(cin + cout + h)
     x = torch.randn(n, cin, h, w, generator=g)
