@@ -65,6 +65,7 @@ _SIGS = {
                         _I, _P, _P],
     "ic2_flrelu_nhwc16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _F,
                           _F, _I, _P, _P],
+    "ic2_flrelu_read_window": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "ic2_fc": [_P, _I64, _P, _P, _P, _I, _I, _I, _F, _F, _I, _F, _F, _P],
     "ic2_pack_weight": [_P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P, _P],
     "ic2_modconv_prep": [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P],
@@ -79,6 +80,7 @@ _SIGS = {
     "ic2_conv_wino": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _F, _F, _F, _I, _P],
     "ic2_conv_wino_plan": [_I, _I, _I, _I, _I, _I],
     "ic2_conv_wino_preferred": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
+    "ic2_conv_wino_rounds": [_I, _I, _I, _I, _I, _I],
     "ic2_synth_input_features": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _I, _P],
     "ic2_nchw_to_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "ic2_from_rgb_conv": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P],
@@ -210,11 +212,25 @@ def wino_plan(n, h, w, cin_p, cout_p, pad):
     return query("ic2_conv_wino_plan", n, h, w, cin_p, cout_p, pad).decode()
 
 
+def wino_rounds(n, h, w, cin_p, cout_p, pad):
+    """Rounds of one workgroup per CU of the ic2_conv_wino launch plan for this geometry."""
+    return int(query("ic2_conv_wino_rounds", n, h, w, cin_p, cout_p, pad))
+
+
 def conv_wino(x, u, y, dtype, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, pad, ho, wo, oscale, bias, act, slope,
               act_gain, clamp, out_mul, out_layout, stream):
     """ic2_conv_wino: the 3x3 conv as a fused Winograd F(2,3) along x (f16 operands; u from ic2_pack_weight_wino)."""
     return call("ic2_conv_wino", x, u, y, dtype, out_dtype, n, h, w_, cin_p, cout_p, cout_valid, pad, ho, wo, oscale,
                 bias, act, slope, act_gain, clamp, out_mul, out_layout, stream)
+
+
+def read_window(in_size, out_size, up, down, up_taps, down_taps, pad_lo, pad_hi, out_first=None, out_last=None):
+    """ic2_flrelu_read_window for one axis: ((first, last) input reaching any output, (first, last) input reaching
+    outputs out_first .. out_last; default: all of them).  A conv axis: up = down = 1, up_taps = k, down_taps = 1."""
+    win = (ctypes.c_int * 4)()
+    call("ic2_flrelu_read_window", in_size, out_size, up, down, up_taps, down_taps, pad_lo, pad_hi,
+         0 if out_first is None else out_first, out_size - 1 if out_last is None else out_last, win)
+    return (win[0], win[1]), (win[2], win[3])
 
 
 _flops_hook = None   # installed by bench.py's instrumented pass: receives each conv's algorithmic FLOPs

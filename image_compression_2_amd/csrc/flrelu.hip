@@ -483,3 +483,32 @@ extern "C" int ic2_flrelu_nhwc16(const void* x, void* y, int dtype_in, int dtype
                        fd_taps, b, up, down, px0, px1, py0, py1, gain, slope, clamp, flip, post_scale, stream,
                        "flrelu_nhwc16", true);
 }
+
+// Host only.  One axis of the op chain zero-insert (up) -> pad / crop (pad_lo, pad_hi) -> FIR up_taps -> FIR down_taps
+// -> keep every down-th: output o reads padded positions o * down .. o * down + up_taps + down_taps - 2, and input i
+// sits at padded position i * up + pad_lo.  A conv axis is the same chain with up = down = 1, up_taps = k,
+// down_taps = 1 and its padding.
+extern "C" int ic2_flrelu_read_window(int in, int out, int up, int down, int up_taps, int down_taps, int pad_lo,
+                                      int pad_hi, int out_first, int out_last, int* win) {
+  IC2_CHECK_ARG(win, "flrelu_read_window: null pointer");
+  IC2_CHECK_ARG(in > 0 && up >= 1 && down >= 1 && up_taps >= 1 && down_taps >= 1, "flrelu_read_window: bad geometry");
+  const int span = up_taps + down_taps - 2;
+  const int64_t len = (int64_t)in * up + pad_lo + pad_hi - span;  // positions a window can start at
+  IC2_CHECK_ARG(len > 0 && out == (len + down - 1) / down, "flrelu_read_window: output %d does not match the geometry",
+                out);
+  IC2_CHECK_ARG(0 <= out_first && out_first <= out_last && out_last < out, "flrelu_read_window: outputs %d..%d of %d",
+                out_first, out_last, out);
+  // consecutive windows must overlap or touch on the input grid, or the reached set has holes
+  IC2_CHECK_ARG(span + 1 >= down && span + 1 >= up, "flrelu_read_window: taps shorter than a stride");
+  auto floor_div = [](int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+  auto range = [&](int o0, int o1, int* r) {
+    const int64_t lo = -floor_div(-((int64_t)o0 * down - pad_lo), up);          // ceil
+    const int64_t hi = floor_div((int64_t)o1 * down + span - pad_lo, up);
+    r[0] = (int)(lo < 0 ? 0 : lo);
+    r[1] = (int)(hi > in - 1 ? in - 1 : hi);
+  };
+  range(0, out - 1, win);
+  range(out_first, out_last, win + 2);
+  IC2_CHECK_ARG(win[0] <= win[1] && win[2] <= win[3], "flrelu_read_window: no input reaches the outputs");
+  return IC2_OK;
+}

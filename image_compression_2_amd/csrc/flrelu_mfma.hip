@@ -588,7 +588,11 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
     const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(yout + (int64_t)n * a.out_h * a.out_w * a.c_p + (BLK ? (int64_t)c0 * a.out_h * a.out_w : (int64_t)c0)), 0,
         FM_OOB, 0x00020000);
-    const int kend = 2 * nt;  // blocks 0 .. kend
+    // Output row r of a tile reads grid rows 2r .. 2r + 11 of it, so the tile's second block (rows 32 .. 47) feeds rows
+    // r >= 11 only: when the image's last tile has at most 11 live rows (every SG3 height but 256 leaves 4), the item
+    // that ends with it stops one block early (uniform per item).  Every wait, DMA and hand-over below is keyed on kend.
+    const bool tail_skip = t0 + nt == a.tiles_y && a.out_h - 16 * (a.tiles_y - 1) <= 11;
+    const int kend = 2 * nt - (tail_skip ? 1 : 0);  // blocks 0 .. kend
 
     fm_f4 acc_a[OCW], acc_b[OCW];
     // store tile t0 + tt from acc_a: lane (g, oy = li) holds channels c0 + 4g .. +3 of output pixel (oy, ox); exactly
@@ -633,9 +637,12 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
     };
     // grid block k of the item: vertical up (ring -> V), horizontal up / activation / down (V -> D), vertical down
     // (D -> acc).  MODE 0: block 0, starts acc_b; 1: odd block, acc_a = acc_b + its share; 2: even block >= 2,
-    // finishes acc_a and starts acc_b for the next tile.  A finished tile is stored at the end of its even block.
-    auto block = [&](int k, auto mode_c) __attribute__((always_inline)) {
+    // finishes acc_a and starts acc_b for the next tile.  A finished tile is stored at the end of its even block (the
+    // image's last tile after its odd block, under tail_skip).
+    // END: the block may be the item's last (k == kend): an even block, or the odd block that ends a tail_skip item
+    auto block = [&](int k, auto mode_c, auto end_c) __attribute__((always_inline)) {
       constexpr int MODE = decltype(mode_c)::value;
+      constexpr bool END = decltype(end_c)::value;
       {  // vertical up
         constexpr int NC = (NINX + NW - 1) / NW;
         // column x = wave + NW i: one per-lane base per block and immediate offsets.  Columns past NINX - 1 (the
@@ -660,7 +667,7 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
       }
       __syncthreads();  // V complete; the ring group k is dead; v-down k-1 done
       // the item's last block: every ring group is dead -> the next item's first rows
-      if (k == kend && has_next) load_item(w + gridDim.x);
+      if (END && k == kend && has_next) load_item(w + gridDim.x);
       // the rows block k+2 needs go out now, into the slot of group k (every wave's vertical up of block k is done):
       // they land behind this block's horizontal pass and vertical down and the next block's vertical up
       const bool dma = k + 2 <= kend;
@@ -768,11 +775,16 @@ __global__ void __launch_bounds__(64 * NW, 32 / NW) flrelu_mfma3_kernel(FlrArgs 
       }
     };
 
-    block(0, std::integral_constant<int, 0>{});
-    for (int t = 0; t < nt; ++t) {
-      block(2 * t + 1, std::integral_constant<int, 1>{});
-      block(2 * t + 2, std::integral_constant<int, 2>{});
+    block(0, std::integral_constant<int, 0>{}, std::false_type{});
+    const int nfull = nt - (tail_skip ? 1 : 0);
+    for (int t = 0; t < nfull; ++t) {
+      block(2 * t + 1, std::integral_constant<int, 1>{}, std::false_type{});
+      block(2 * t + 2, std::integral_constant<int, 2>{}, std::true_type{});
       store_tile(t);
+    }
+    if (tail_skip) {  // the image's last tile: acc_a is complete after its odd block
+      block(kend, std::integral_constant<int, 1>{}, std::true_type{});
+      store_tile(nt - 1);
     }
   }
 }

@@ -561,6 +561,13 @@ extern "C" const char* ic2_conv_wino_plan(int n, int h, int w_, int cin_p, int c
   return buf;
 }
 
+extern "C" int ic2_conv_wino_rounds(int n, int h, int w_, int cin_p, int cout_p, int pad) {
+  const int ho = h + 2 * pad - 2, wo = w_ + 2 * pad - 2;
+  if (n <= 0 || ho <= 0 || wo <= 0 || cin_p <= 0 || cin_p % 32 || cout_p <= 0 || cout_p % 32) return -1;
+  const int nc = conv_chunk_n(IC2_F16, n, h, w_, cin_p);
+  return (int)(wx_tile(nc, ho, wo, cout_p).rounds() * ceil_div(n, nc));
+}
+
 extern "C" int ic2_conv_wino(const void* x, const void* u, void* y, int dtype, int out_dtype, int n, int h, int w_,
                              int cin_p, int cout_p, int cout_valid, int pad, int ho, int wo, const float* oscale,
                              const float* bias, int act, float slope, float act_gain, float clamp, float out_mul,

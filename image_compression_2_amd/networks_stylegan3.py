@@ -42,6 +42,10 @@ _FLR_BLOCKED = nv.knob("IC2_FLR_BLOCKED", 1) != 0
 # filtered lrelu -> conv hand-off channel-blocked too, on the no-grad 16-bit synthesis path, wherever the next layer's
 # conv kernel reads it that way (ic2_conv_accepts_nhwc16); False (knob IC2_ACT_BLOCKED=0 under IC2_DEV=1): plain NHWC
 _ACT_BLOCKED = nv.knob("IC2_ACT_BLOCKED", 1) != 0
+# no-grad 16-bit synthesis: a conv leaves out the border rows and columns its filtered lrelu never reads
+# (ic2_flrelu_read_window) on the layers SynthesisNetwork.trim_plan picks; False: the reference geometry everywhere.
+# The image is bit-identical either way.
+_SYNTH_TRIM = True
 # longest row (w_dim, cin) of ic2_modconv_prep_batched's LDS-staged small GEMM (synth_ops.hip kSmK)
 _MOD_BATCH_MAX = 512
 
@@ -64,6 +68,15 @@ def _refuse(module, out, *tensors):
 
 def _version_key(*tensors):
     return tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+
+
+class LayerTrim:
+    """Launch geometry of a synthesis layer whose conv leaves out `border` rows and columns per side that its filtered
+    lrelu never reads (SynthesisLayer.trimmed): the conv's padding, and the filtered lrelu's padding on that smaller
+    conv output.  Input and output sizes stay the layer's."""
+
+    def __init__(self, border, conv_pad, flr_padding):
+        self.border, self.conv_pad, self.flr_padding = border, conv_pad, flr_padding
 
 
 # ------------------------------------------------------------------------------------------------
@@ -383,18 +396,38 @@ class SynthesisLayer(torch.nn.Module):
         return xs, os_
 
     # ---- NHWC pipeline step ------------------------------------------------------------------
-    def takes_blocked_input(self, n, dt):
+    def takes_blocked_input(self, n, dt, trim=None):
         """True when this layer's conv reads its input channel-blocked ([n, cin_p/16, in, in, 16]) on the no-grad
-        16-bit path: the library's predicate for the kernel the launch plan picks, under the module switch."""
+        16-bit path: the library's predicate for the kernel the launch plan picks (asked with the geometry that is
+        launched: trim, a LayerTrim), under the module switch."""
         if not _ACT_BLOCKED or dt not in (torch.bfloat16, torch.float16):
             return False
         s_in, k = int(self.in_size[0]), self.conv_kernel
+        pad = k - 1 if trim is None else trim.conv_pad
         if self.is_torgb:
             out_dt, layout = nv.F32, nv.NCHW
         else:
             out_dt, layout = nv.F16, (nv.NHWC16 if _FLR_BLOCKED else nv.NHWC)
         return nv.conv_accepts_nhwc16(nv.dtype_code(dt), out_dt, layout, n, s_in, s_in, self.cin_p, self.cout_p,
-                                      self.out_channels, k, k, k - 1)
+                                      self.out_channels, k, k, pad)
+
+    def unread_border(self):
+        """Rows and columns per side of the conv output (padding k - 1) that no output of the filtered lrelu reads
+        (ic2_flrelu_read_window), at most the k - 1 that the conv's padding produces."""
+        s_conv, s_out, k = int(self.in_size[0]) + self.conv_kernel - 1, int(self.out_size[0]), self.conv_kernel
+        if self.is_torgb or self.padding[:2] != self.padding[2:]:
+            return 0
+        (first, last), _ = nv.read_window(s_conv, s_out, self.up_factor, self.down_factor, self.up_taps,
+                                          self.down_taps, *self.padding[:2])
+        return min(first, s_conv - 1 - last, k - 1)
+
+    def trimmed(self, border):
+        """LayerTrim for a conv that leaves out `border` (<= unread_border()) rows and columns per side, or None for 0:
+        the conv pads that much less, and the filtered lrelu's padding grows by up per dropped row and column."""
+        if border <= 0:
+            return None
+        assert border <= self.unread_border()
+        return LayerTrim(border, self.conv_kernel - 1 - border, [p + border * self.up_factor for p in self.padding])
 
     def writes_blocked_output(self, dt):
         """True when this layer's filtered lrelu has the strip MFMA instance that writes the channel-blocked layout
@@ -403,10 +436,11 @@ class SynthesisLayer(torch.nn.Module):
                 and self.down_factor == 2 and self._fu is not None and self._fd is not None
                 and self._fu.shape[0] == 6 * self.up_factor and self._fd.shape[0] == 12)
 
-    def run_nhwc(self, x, n, dt, oscale, post_scale, final_scale=None, x_blocked=False, out_blocked=False):
+    def run_nhwc(self, x, n, dt, oscale, post_scale, final_scale=None, x_blocked=False, out_blocked=False, trim=None):
         """x: NHWC [n, in, in, cin_p] (x_blocked: [n, cin_p/16, in, in, 16]) already scaled by this layer's xscale.
         Returns NHWC (out_blocked: channel-blocked) output scaled by post_scale (next layer's xscale), or -- for
-        ToRGB -- the final NCHW f32 image * final_scale."""
+        ToRGB -- the final NCHW f32 image * final_scale.  trim (a LayerTrim): the conv leaves out the border the
+        filtered lrelu never reads, same output bit for bit; the conv FLOPs announced stay the reference's."""
         s_in = int(self.in_size[0])
         k = self.conv_kernel
         pad = k - 1
@@ -416,7 +450,7 @@ class SynthesisLayer(torch.nn.Module):
         nv.note_flops(2 * n * conv * conv * self.out_channels * self.in_channels * k * k)
         in_flag = nv.act_in_layout(nv.NHWC16) if x_blocked else 0  # the input layout rides above the conv's `act`
         if self.is_torgb:
-            assert self.up_factor == 1 and self.down_factor == 1 and self.padding == [0, 0, 0, 0]
+            assert self.up_factor == 1 and self.down_factor == 1 and self.padding == [0, 0, 0, 0] and trim is None
             out = torch.empty([n, self.out_channels, conv, conv], dtype=torch.float32, device=x.device)
             clamp = float(self.conv_clamp) if self.conv_clamp is not None else -1.0
             nv.conv_igemm(nv.ptr(x), nv.ptr(wp), nv.ptr(out), nv.dtype_code(dt), nv.F32, n, s_in, s_in, self.cin_p,
@@ -424,15 +458,16 @@ class SynthesisLayer(torch.nn.Module):
                           nv.ACT_LRELU | in_flag, 1.0, 1.0, clamp,
                           float(1.0 if final_scale is None else final_scale), nv.NCHW, stream, x.device)
             return out
-        y, blocked = self.conv_nhwc(x, n, dt, oscale, x_blocked=x_blocked)
-        return self.flrelu_nhwc(y, dt, post_scale, blocked=blocked, out_blocked=out_blocked)
+        y, blocked = self.conv_nhwc(x, n, dt, oscale, x_blocked=x_blocked, trim=trim)
+        return self.flrelu_nhwc(y, dt, post_scale, blocked=blocked, out_blocked=out_blocked, trim=trim)
 
-    def conv_nhwc(self, x, n, dt, oscale, x_blocked=False):
+    def conv_nhwc(self, x, n, dt, oscale, x_blocked=False, trim=None):
         """The modulated conv of a non-ToRGB layer (x_blocked: the input is channel-blocked, for a layer whose
-        takes_blocked_input is true): -> (conv output y, blocked layout?) for flrelu_nhwc."""
+        takes_blocked_input is true): -> (conv output y, blocked layout?) for flrelu_nhwc.  trim: the conv runs with
+        the padding trim.conv_pad, y is that much smaller."""
         s_in = int(self.in_size[0])
         k = self.conv_kernel
-        pad = k - 1
+        pad = k - 1 if trim is None else trim.conv_pad
         conv = s_in + 2 * pad - k + 1
         wp, _, bp = self.packed(dt)
         stream = nv.stream_of(x)
@@ -472,10 +507,11 @@ class SynthesisLayer(torch.nn.Module):
         self._cache["wino"] = (key, u)
         return u
 
-    def flrelu_nhwc(self, y, dt_out, post_scale=None, blocked=False, out_blocked=False):
+    def flrelu_nhwc(self, y, dt_out, post_scale=None, blocked=False, out_blocked=False, trim=None):
         """The layer's filtered lrelu on the conv output y NHWC [n, conv, conv, cout_p] (f32, or f16 for the
         MFMA kernel; blocked: f16/bf16 [n, cout_p/16, conv, conv, 16]) -> NHWC [n, out, out, cout_p] dt_out (out_blocked:
-        [n, cout_p/16, out, out, 16], the strip MFMA kernel only), times post_scale [n][cout_p] when given."""
+        [n, cout_p/16, out, out, 16], the strip MFMA kernel only), times post_scale [n][cout_p] when given.
+        trim: y is the trimmed conv output, read with the padding trim.flr_padding."""
         n, conv = y.shape[0], y.shape[2 if blocked else 1]
         s_out = int(self.out_size[0])
         if out_blocked:
@@ -484,7 +520,7 @@ class SynthesisLayer(torch.nn.Module):
             out = torch.empty([n, s_out, s_out, self.cout_p], dtype=dt_out, device=y.device)
         fu = self._fu
         fd = self._fd
-        px0, px1, py0, py1 = self.padding
+        px0, px1, py0, py1 = self.padding if trim is None else trim.flr_padding
         clamp = float(self.conv_clamp) if self.conv_clamp is not None else -1.0
         nv.call("ic2_flrelu_nhwc16" if blocked else "ic2_flrelu_nhwc", nv.ptr(y), nv.ptr(out), nv.dtype_code(y.dtype),
                 nv.dtype_code(dt_out) | (nv.flr_out_layout(nv.NHWC16) if out_blocked else 0), n,
@@ -700,15 +736,42 @@ class SynthesisNetwork(torch.nn.Module):
         sc = self.scales_batched(ws, ldx, n, dt)
         x = self.input.run_nhwc(ws, ldx, n, dt, sc[0][0])
         x_blocked = False
+        trim = self.trim_plan(n, dt)
         for i, L in enumerate(layers):
             post = sc[i + 1][0] if i + 1 < len(layers) else None
             # the activation stays channel-blocked exactly where the next layer's conv reads it that way
             out_blocked = (i + 1 < len(layers) and L.writes_blocked_output(dt)
-                           and layers[i + 1].takes_blocked_input(n, dt))
+                           and layers[i + 1].takes_blocked_input(n, dt, trim=trim[i + 1]))
             x = L.run_nhwc(x, n, dt, sc[i][1], post, final_scale=self.output_scale if L.is_torgb else None,
-                           x_blocked=x_blocked, out_blocked=out_blocked)
+                           x_blocked=x_blocked, out_blocked=out_blocked, trim=trim[i])
             x_blocked = out_blocked
         return _refuse(self, x, ws_in)
+
+    def trim_plan(self, n, dt):
+        """[LayerTrim, or None: the reference geometry] per layer of the no-grad 16-bit path at batch n.  A layer's conv
+        leaves out the border its filtered lrelu never reads where the reference and the trimmed geometry both run the
+        Winograd kernel and the trimmed launch plan takes fewer rounds of workgroups (SG3-T-256 at batch 32: L5, L7).
+        Bits first, then time: the implicit-GEMM plans split K, or run a half-K tail, depending on the pixel count, so
+        a smaller launch sums some pixels in another order (L3 at batch 32); the hg4 layer L13 and the Winograd
+        launches of equal rounds (L10) measured level.  DESIGN.md, Winograd section."""
+        if not _SYNTH_TRIM or dt not in (torch.bfloat16, torch.float16):
+            return [None] * len(self.layer_names)
+        cache = self.__dict__.setdefault("_trim_plans", {})   # planned once per (batch, dtype)
+        if (n, dt) in cache:
+            return cache[n, dt]
+        plan = []
+        for L in self.layers():
+            T = None if L.is_torgb else L.trimmed(L.unread_border())
+            if T is not None:
+                s_in, k = int(L.in_size[0]), L.conv_kernel
+                wino = all(nv.wino_preferred(nv.dtype_code(dt), n, s_in, s_in, L.cin_p, L.cout_p, k, k, pad)
+                           for pad in (k - 1, T.conv_pad))
+                if not (wino and nv.wino_rounds(n, s_in, s_in, L.cin_p, L.cout_p, T.conv_pad)
+                        < nv.wino_rounds(n, s_in, s_in, L.cin_p, L.cout_p, k - 1)):
+                    T = None
+            plan.append(T)
+        cache[n, dt] = plan
+        return plan
 
     def scales_batched(self, ws, ldx, n, dt):
         """[(xscale [n][cin_p], oscale [n][cout_p]) per layer] through ic2_modconv_prep_batched (per layer when a

@@ -179,6 +179,16 @@ int ic2_flrelu_nhwc16(const void* x, void* y, int dtype_in, int dtype_out, int n
                       int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, float clamp,
                       int flip, const float* post_scale, void* stream);
 
+/* Host only (no GPU): which inputs one axis of the filtered lrelu reads.  The axis has `in` samples, `out` outputs (as
+ * the entry points above expect them for this padding), factors up / down, up_taps / down_taps FIR taps (every tap
+ * counted as non-zero) and padding (pad_lo, pad_hi), negative = crop.  win[0], win[1]: first and last input index that
+ * reach any output; win[2], win[3]: the same for outputs out_first .. out_last only.  A conv axis is the same chain
+ * with up = down = 1, up_taps = k, down_taps = 1.  The synthesis trims its launches to these windows: dropping `lo`
+ * leading and `hi` trailing inputs outside a window and adding lo * up, hi * up to the padding leaves the outputs
+ * unchanged; so does launching outputs a .. out-1-a' alone with the padding lowered by a * down, a' * down. */
+int ic2_flrelu_read_window(int in, int out, int up, int down, int up_taps, int down_taps, int pad_lo, int pad_hi,
+                           int out_first, int out_last, int* win);
+
 /* ----------------------------------------------------------------- modulated conv (MFMA) ---- */
 
 /* FullyConnectedLayer.forward [SG3-public] and nn.Linear (stylegan3_hvae_full.py:206-234):
@@ -285,6 +295,10 @@ int ic2_conv_wino_preferred(int dtype, int n, int h, int w_, int cin_p, int cout
 
 /* ic2_conv_wino's launch plan for a geometry, e.g. "wino_fx_o128_p15x8_f16" (tile: 15 pairs x 8 rows).  Host only. */
 const char* ic2_conv_wino_plan(int n, int h, int w_, int cin_p, int cout_p, int pad);
+
+/* Rounds of one workgroup per CU that plan takes (the planner's own cost of a tile; -1: invalid geometry).  Host only.
+ * The synthesis runs a conv without the border its filtered lrelu never reads where that saves a round. */
+int ic2_conv_wino_rounds(int n, int h, int w_, int cin_p, int cout_p, int pad);
 
 /* SynthesisInput.forward Fourier features [SG3-public]: t [n][4] = affine(w); per sample the
  * rotation/translation of freqs/phases, the amplitude damping and sin(2*pi*(grid.f + phi)) * amp on a
