@@ -77,6 +77,14 @@ __device__ __forceinline__ float lrelu_gain_clamp(float v, float slope, float ga
   return v;
 }
 
+// The reference's uint8 image conversion (hvae_training.py:368-388), shared by the PSNR and SSIM kernels.
+__device__ __forceinline__ int to_u8(float v) {
+#pragma clang fp contract(off)  // (x * 0.5 + 0.5) as two roundings
+  float t = v * 0.5f + 0.5f;
+  t = fminf(fmaxf(t, 0.f), 1.f);
+  return (int)(t * 255.f);  // truncation, as numpy astype(np.uint8) on [0, 255]
+}
+
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // A zeroed 64-byte line in the code object: out-of-image loads read it instead of branching around

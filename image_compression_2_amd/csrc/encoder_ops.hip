@@ -444,13 +444,6 @@ __global__ void __launch_bounds__(256) reparam_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int to_u8(float v) {
-#pragma clang fp contract(off)  // (x * 0.5 + 0.5) as two roundings (hvae_training.py:368-388)
-  float t = v * 0.5f + 0.5f;
-  t = fminf(fmaxf(t, 0.f), 1.f);
-  return (int)(t * 255.f);  // truncation, as numpy astype(np.uint8) on [0, 255]
-}
-
 // stage 1: per (image, chunk) partial sums (each thread: float4 loads, exact integer squares summed in
 // f64); stage 2: per image ordered sum over the chunks.  Deterministic, no atomics.
 constexpr int SSE_CHUNKS = 64;

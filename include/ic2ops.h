@@ -370,6 +370,19 @@ int64_t ic2_uint8_sse_scratch_doubles(int64_t n_img);
 int ic2_uint8_sse(const float* a, const float* b, int64_t n_img, int64_t per_img, double* sse_out, double* scratch,
                   void* stream);
 
+/* PSNR + SSIM support in one pass over both images (hvae_training.py:382-395: skimage peak_signal_noise_ratio and
+ * structural_similarity(channel_axis=2, data_range=255) of the uint8 images).  a, b: NCHW f32 [n_img][c][h][w],
+ * converted as above.  sse_out [n_img] (f64): as ic2_uint8_sse.  ssim_sum_out [n_img * c] (f64): per (image, channel)
+ * the sum of the SSIM map S over the (h-win+1)*(w-win+1) windows that lie fully inside the image (what skimage's
+ * crop(S, (win-1)//2).mean() averages); uniform win x win window, win odd in [3, 11] (skimage default 7), sample
+ * covariance, K1 = 0.01, K2 = 0.03.  The window moments are exact integers and S is formed in f64; the division by
+ * the window count and the channel mean are the caller's.  Deterministic: per-tile partials in
+ * scratch (ic2_uint8_quality_scratch_doubles doubles; 0 for an invalid shape), summed in a fixed order, no atomics.
+ * IC2_E_INVALID: null pointer, non-positive size, win even or outside [3, 11], h < win or w < win. */
+int64_t ic2_uint8_quality_scratch_doubles(int64_t n_img, int c, int h, int w, int win);
+int ic2_uint8_quality(const float* a, const float* b, int64_t n_img, int c, int h, int w, int win, double* sse_out,
+                      double* ssim_sum_out, double* scratch, void* stream);
+
 /* F.interpolate(mode='bilinear', align_corners=False, no antialias) of StyleGAN3Compressor.forward
  * (stylegan3_hvae_full.py:277-279), NCHW f32. */
 int ic2_resize_bilinear(const float* x, float* y, int64_t nc, int h, int w, int oh, int ow, void* stream);
