@@ -567,7 +567,10 @@ __global__ void __launch_bounds__(256) code_record_kernel(const void* __restrict
     bool diff = false;
     if constexpr (KIND == 0) {
       const float q = reinterpret_cast<const float*>(codes)[i];
-      c = (int64_t)rintf(((q + 1.0f) * 0.5f) * S);
+      // a NaN / +-inf latent (or one far off the grid) is not a code: the range test is made on the float, where it is
+      // false for NaN, instead of on the converted integer (the conversion of such a value is unspecified)
+      const float v = rintf(((q + 1.0f) * 0.5f) * S);
+      c = (v >= 0.0f && v < (float)k) ? (int64_t)v : -1;
       if (golden) diff = __float_as_uint(q) != __float_as_uint(reinterpret_cast<const float*>(golden)[i]);
     } else {
       c = reinterpret_cast<const int64_t*>(codes)[i];

@@ -124,8 +124,8 @@ int ic2_gumbel_noise(const int64_t* seed_dev, uint64_t seed, uint64_t offset, in
 /* Per-batch code record (SURVEY.md 8e metric record; usage / perplexity over the batch,
  * gumbel_softmax_compression.py:121-127): kind 0 = f32 latents from ic2_quantize_uniform at `bits` (code =
  * round((q + 1) * 0.5 * (2^bits - 1)), k = 2^bits), kind 1 = int64 codebook indices (k codes).  counts uint32 [k + 2],
- * zeroed by the caller: += hist[0 .. k), codes outside [0, k) in counts[k], elements differing from golden (nullable,
- * same kind; bitwise for kind 0) in counts[k + 1]. */
+ * zeroed by the caller: += hist[0 .. k), codes outside [0, k) in counts[k] (a NaN or infinite latent is no code and is
+ * counted there), elements differing from golden (nullable, same kind; bitwise for kind 0) in counts[k + 1]. */
 int ic2_code_record(const void* codes, int kind, int k, int bits, const void* golden, int64_t n, uint32_t* counts,
                     void* stream);
 

@@ -131,6 +131,36 @@ def test_conv_backward_kernels(cuda, cin, cout, size, pad, n, dtype):
     assert _rel(bd.grad, br.grad) < tol
 
 
+@pytest.mark.parametrize("cin,cout,h,w,pad,n", [(40, 70, 9, 15, 1, 2), (32, 64, 13, 5, 0, 3)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_conv_backward_kernels_nonsquare(cuda, cin, cout, h, w, pad, n, dtype):
+    """The same check with h != w (a swapped height / width in the data gradient's geometry passes every square
+    case), and with cin < cin_p and cout < cout_p together."""
+    g = torch.Generator().manual_seed(cin * 7 + cout + h)
+    x = torch.randn(n, cin, h, w, generator=g)
+    wt = torch.randn(cout, cin, 3, 3, generator=g) / np.sqrt(9 * cin)
+    b = torch.randn(cout, generator=g)
+    dy = torch.randn(n, cout, h + 2 * pad - 2, w + 2 * pad - 2, generator=g)
+    cin_p, cout_p = nv.pad32(cin), nv.pad32(cout)
+    xd = ao.ToNHWC.apply(x.to(cuda), dtype, cin_p).detach().requires_grad_(True)
+    wd, bd = wt.to(cuda).requires_grad_(True), b.to(cuda).requires_grad_(True)
+    with torch.enable_grad():
+        y = ao.Conv2dNHWC.apply(xd, wd, bd, pad, cout_p)
+        assert y.shape == (n, h + 2 * pad - 2, w + 2 * pad - 2, cout_p)
+        y.backward(F.pad(dy.permute(0, 2, 3, 1), (0, cout_p - cout)).to(cuda, dtype))
+    xr = x.to(dtype).double().requires_grad_(True)
+    wr = wt.to(dtype).double().requires_grad_(True) if dtype != torch.float32 else wt.double().requires_grad_(True)
+    br = b.double().requires_grad_(True)
+    F.conv2d(xr, wr, br, padding=pad).backward(dy.to(dtype).double())
+    tol = {torch.float32: 1e-5, torch.bfloat16: 2e-2, torch.float16: 3e-3}[dtype]
+    assert xd.grad.shape == (n, h, w, cin_p)
+    assert _rel(xd.grad.float().cpu()[..., :cin].permute(0, 3, 1, 2), xr.grad) < tol
+    if cin < cin_p:
+        assert xd.grad.float()[..., cin:].abs().max().item() == 0.0
+    assert _rel(wd.grad, wr.grad) < tol
+    assert _rel(bd.grad, br.grad) < tol
+
+
 @pytest.mark.parametrize("n,c,groups,h,w,pool", [(2, 64, 32, 6, 8, True), (3, 32, 32, 9, 7, False),
                                                  (2, 128, 32, 5, 5, True), (1, 512, 32, 2, 2, True),
                                                  (2, 96, 32, 33, 17, False)])
