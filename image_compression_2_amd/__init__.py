@@ -4,7 +4,7 @@ Drop-in classes (same names / signatures as the reference modules):
   stylegan3_hvae_full:        HVAE_VGG_Encoder, VGGBlock, HierarchyProjector, StyleGAN3Compressor,
                               save_tensor_as_image
   gumbel_softmax_compression: GumbelSoftmaxDiscretization, GumbelSoftmaxCompressor
-  networks_stylegan3:         Generator (G_ema duck type), SynthesisNetwork, SynthesisLayer, ...
+  networks_stylegan3:         Generator (G_ema duck type; T, and R with SG3_R_KWARGS), SynthesisNetwork, ...
   sg3_ops:                    bias_act, upfirdn2d, filtered_lrelu  (torch_utils.ops mirrors)
   cabac_compression:          ContextModel, cabac_encode / cabac_decode, CABACCompressor (native range coder)
   legacy:                     load_network_pkl (SG3 pickle loader that executes nothing from the file)
@@ -16,7 +16,7 @@ from .stylegan3_hvae_full import (HVAE_VGG_Encoder, VGGBlock, HierarchyProjector
                                   save_tensor_as_image, quantize_uniform, resize_bilinear)
 from .gumbel_softmax_compression import GumbelSoftmaxDiscretization, GumbelSoftmaxCompressor  # noqa: F401
 from .networks_stylegan3 import (Generator, SynthesisNetwork, SynthesisLayer, SynthesisInput,  # noqa: F401
-                                 MappingNetwork, FullyConnectedLayer, make_generator)
+                                 MappingNetwork, FullyConnectedLayer, make_generator, SG3_R_KWARGS)
 from . import sg3_ops  # noqa: F401
 from .cabac_compression import CABACCompressor, ContextModel, cabac_encode, cabac_decode  # noqa: F401
 from . import legacy  # noqa: F401
@@ -24,6 +24,6 @@ from .metrics import uint8_quality, ssim, ssim_from_sums, evaluate_compression  
 
 __all__ = ["HVAE_VGG_Encoder", "VGGBlock", "HierarchyProjector", "StyleGAN3Compressor", "save_tensor_as_image",
            "GumbelSoftmaxDiscretization", "GumbelSoftmaxCompressor", "Generator", "SynthesisNetwork",
-           "SynthesisLayer", "SynthesisInput", "MappingNetwork", "FullyConnectedLayer", "make_generator",
+           "SynthesisLayer", "SynthesisInput", "MappingNetwork", "FullyConnectedLayer", "make_generator", "SG3_R_KWARGS",
            "quantize_uniform", "resize_bilinear", "sg3_ops", "CABACCompressor", "ContextModel", "cabac_encode",
            "cabac_decode", "legacy", "uint8_quality", "ssim", "ssim_from_sums", "evaluate_compression"]

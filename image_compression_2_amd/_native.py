@@ -65,6 +65,10 @@ _SIGS = {
                         _I, _P, _P],
     "ic2_flrelu_nhwc16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _F,
                           _F, _I, _P, _P],
+    "ic2_flrelu_nhwc_2d": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I,
+                           _F, _F, _F, _I, _P, _P],
+    "ic2_flrelu_nhwc16_2d": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I,
+                             _I, _F, _F, _F, _I, _P, _P],
     "ic2_flrelu_read_window": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "ic2_fc": [_P, _I64, _P, _P, _P, _I, _I, _I, _F, _F, _I, _F, _F, _P],
     "ic2_pack_weight": [_P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P, _P],

@@ -17,8 +17,8 @@ pickle stores every network as a ``torch_utils.persistence`` record: ``_reconstr
 
 ``load_network_pkl(f)`` returns ``{'G_ema': Generator, ...}`` (other top-level entries as raw records) so
 ``load_network_pkl(f)['G_ema']`` is the drop-in for the reference line.  The generator is this package's
-``Generator`` (SG3-T only; radial filters, i.e. SG3-R, are rejected), built from the record's ``_init_kwargs`` and
-filled with ``load_state_dict(strict=True)``.
+``Generator``, built from the record's ``_init_kwargs`` and filled with ``load_state_dict(strict=True)``.  An SG3-R
+record (``use_radial_filters``) is rejected unless the caller passes ``allow_radial=True``: R runs inference only.
 
 Parity: unpinned against a real NVlabs pickle (none is available offline); tests build pickles
 with the same record layout and check the round trip, the allow-list and that injected globals never run.
@@ -175,7 +175,7 @@ def record_state_dict(rec, prefix=""):
     return out
 
 
-def _generator_kwargs(rec):
+def _generator_kwargs(rec, allow_radial=False):
     kw = rec.init_kwargs
     if not kw:   # positional construction: Generator(z_dim, c_dim, w_dim, img_resolution, img_channels, ...)
         names = ["z_dim", "c_dim", "w_dim", "img_resolution", "img_channels"]
@@ -186,36 +186,39 @@ def _generator_kwargs(rec):
             kw[k] = st[k]
     syn = dict(kw.pop("synthesis_kwargs", {}) or {})
     kw.update(syn)
-    if kw.pop("use_radial_filters", False):
-        raise NotImplementedError("StyleGAN3-R (radial filters) is out of scope (DESIGN.md (f)); use an SG3-T pickle")
+    if kw.get("use_radial_filters", False) and not allow_radial:
+        raise NotImplementedError("StyleGAN3-R (radial filters) runs inference only (DESIGN.md, StyleGAN3-R): pass "
+                                  "allow_radial=True to load it, or use an SG3-T pickle")
     return kw
 
 
-def generator_from_record(rec, precision="fp32", device="cuda"):
-    """Build this package's ``Generator`` from a G/G_ema record and load its weights (strict key match)."""
+def generator_from_record(rec, precision="fp32", device="cuda", allow_radial=False):
+    """Build this package's ``Generator`` from a G/G_ema record and load its weights (strict key match).
+    allow_radial: accept an SG3-R record (radial down filters; inference only)."""
     from .networks_stylegan3 import Generator
     if not isinstance(rec, PersistentRecord) or rec.class_name != "Generator":
         raise ValueError(f"expected a persistent Generator record, got {rec!r}")
-    kw = _generator_kwargs(rec)
+    kw = _generator_kwargs(rec, allow_radial)
     G = Generator(precision=precision, **kw)
     sd = record_state_dict(rec)
     G.load_state_dict(sd, strict=True)
     return G.to(device).eval().requires_grad_(False)
 
 
-def load_network_pkl(f, precision="fp32", device="cuda"):
+def load_network_pkl(f, precision="fp32", device="cuda", allow_radial=False):
     """``legacy.load_network_pkl`` / ``pickle.load(f)`` mirror: ``{'G_ema': Generator, 'G': ..., ...}``.
 
     ``f`` is a path or a binary file object.  ``G_ema`` (and ``G`` when present) become ``Generator`` modules on
-    ``device``; other entries (``D``, ``augment_pipe``, ``training_set_kwargs``) are returned as inert records."""
+    ``device``; other entries (``D``, ``augment_pipe``, ``training_set_kwargs``) are returned as inert records.
+    allow_radial: accept SG3-R generators (``generator_from_record``)."""
     if isinstance(f, (str, bytes)) or hasattr(f, "__fspath__"):
         with open(f, "rb") as fh:
-            return load_network_pkl(fh, precision=precision, device=device)
+            return load_network_pkl(fh, precision=precision, device=device, allow_radial=allow_radial)
     data = SafeUnpickler(f).load()
     if not isinstance(data, dict) or "G_ema" not in data:
         raise ValueError("not an SG3 network pickle (no 'G_ema' entry)")
     out = dict(data)
     for k in ("G_ema", "G"):
         if isinstance(out.get(k), PersistentRecord):
-            out[k] = generator_from_record(out[k], precision=precision, device=device)
+            out[k] = generator_from_record(out[k], precision=precision, device=device, allow_radial=allow_radial)
     return out

@@ -1,4 +1,4 @@
-"""MI355X-native StyleGAN3-T generator: the ``G_ema`` duck type the reference decodes with.
+"""MI355X-native StyleGAN3 generator (T, and R for inference): the ``G_ema`` duck type the reference decodes with.
 
 The reference unpickles NVlabs' ``G_ema`` (/root/reference/stylegan3_hvae_full.py:454-455) and calls
 ``G.synthesis(ws, noise_mode=...)`` (``:274, :329``; ``gumbel_softmax_compression.py:193, 262``),
@@ -18,6 +18,10 @@ the filtered lrelu is f16, whose FIR runs on MFMA with f16 operands and fp32 acc
 20 dB more synthesis SNR than bf16 at the same MFMA rate; outputs saturate at +-65504, far above conv_clamp);
 inference only (the autograd path trains in bf16).  ``precision='fp32'`` (default) is the parity mode (exact-fp32 MFMA).
 
+StyleGAN3-R (``SG3_R_KWARGS``: 1x1 convs, twice the channels, radially symmetric 2-D down filters on the non-critical
+layers) runs the same pipeline for inference, its filtered lrelu through ``ic2_flrelu_nhwc_2d``; its autograd path is
+not implemented and raises ``AutogradUnsupported`` before any launch.
+
 With grad mode on and ``ws`` requiring grad (the reference's encoder training backpropagates through the
 frozen generator, :669-696) ``SynthesisNetwork.forward`` takes the autograd path ``forward_train``: the same
 conv / filtered-lrelu kernels with HIP backward passes (autograd_ops), gradients w.r.t. ws only.
@@ -29,6 +33,7 @@ import math
 
 import numpy as np
 import scipy.signal
+import scipy.special
 import torch
 import torch.nn.functional as F
 
@@ -48,6 +53,28 @@ _ACT_BLOCKED = nv.knob("IC2_ACT_BLOCKED", 1) != 0
 _SYNTH_TRIM = True
 # longest row (w_dim, cin) of ic2_modconv_prep_batched's LDS-staged small GEMM (synth_ops.hip kSmK)
 _MOD_BATCH_MAX = 512
+# the StyleGAN3-R configuration of NVlabs' train.py (--cfg=stylegan3-r): Generator(..., **SG3_R_KWARGS)
+SG3_R_KWARGS = dict(conv_kernel=1, channel_base=65536, channel_max=1024, use_radial_filters=True)
+# most separable terms a radial down filter may be split into (ic2ops.h ic2_flrelu_nhwc_2d `rank`)
+_RADIAL_MAX_RANK = 4
+
+
+def radial_rank(f, max_rank=_RADIAL_MAX_RANK):
+    """Separable factorisation of a 2-D down filter f [taps, taps] for ic2_flrelu_nhwc_2d: (R, fv [R, taps], fh [R, taps])
+    float32 with f ~ sum_k outer(fv[k], fh[k]), from the float64 SVD, R the smallest rank whose truncation error is
+    ||f - f_R||_1 <= 2^-11 ||f||_1 (entry-wise 1-norms) -- what rounding the exact taps to f16 operands already costs.
+    R > max_rank: (0, None, None), the filter takes the direct kernel."""
+    f = np.asarray(f, dtype=np.float64)
+    assert f.ndim == 2 and f.shape[0] == f.shape[1], f.shape
+    u, sv, vt = np.linalg.svd(f)
+    bound = 2.0 ** -11 * np.abs(f).sum()
+    for r in range(1, min(max_rank, len(sv)) + 1):
+        fr = (u[:, :r] * sv[:r]) @ vt[:r]
+        if np.abs(f - fr).sum() <= bound:
+            root = np.sqrt(sv[:r])
+            return (r, np.ascontiguousarray((u[:, :r] * root).T, np.float32),
+                    np.ascontiguousarray(vt[:r] * root[:, None], np.float32))
+    return 0, None, None
 
 
 def _train_mode(module, *tensors):
@@ -68,6 +95,10 @@ def _refuse(module, out, *tensors):
 
 def _version_key(*tensors):
     return tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+
+
+_RADIAL_AUTOGRAD = ("training through a StyleGAN3-R generator is not implemented: the filtered lrelu has no backward for "
+                    "a 2-D (radial) down filter.  Run it under torch.no_grad() or detach ws / x (inference only)")
 
 
 class LayerTrim:
@@ -268,8 +299,6 @@ class SynthesisLayer(torch.nn.Module):
                  conv_kernel=3, filter_size=6, lrelu_upsampling=2, use_radial_filters=False, conv_clamp=256,
                  magnitude_ema_beta=0.999):
         super().__init__()
-        if use_radial_filters and not is_critically_sampled and not is_torgb:
-            raise NotImplementedError("radial (StyleGAN3-R) filters are not on the path: StyleGAN3-T only")
         self.w_dim = w_dim
         self.is_torgb = is_torgb
         self.is_critically_sampled = is_critically_sampled
@@ -303,9 +332,10 @@ class SynthesisLayer(torch.nn.Module):
         self.down_factor = int(np.rint(self.tmp_sampling_rate / self.out_sampling_rate))
         assert self.out_sampling_rate * self.down_factor == self.tmp_sampling_rate
         self.down_taps = filter_size * self.down_factor if self.down_factor > 1 and not self.is_torgb else 1
-        self.down_radial = use_radial_filters and not self.is_critically_sampled
+        self.down_radial = bool(use_radial_filters and not self.is_critically_sampled and self.down_taps > 1)
         self.register_buffer("down_filter", self.design_lowpass_filter(
-            numtaps=self.down_taps, cutoff=self.out_cutoff, width=self.out_half_width * 2, fs=self.tmp_sampling_rate))
+            numtaps=self.down_taps, cutoff=self.out_cutoff, width=self.out_half_width * 2, fs=self.tmp_sampling_rate,
+            radial=self.down_radial))
 
         pad_total = (self.out_size - 1) * self.down_factor + 1
         pad_total -= (self.in_size + self.conv_kernel - 1) * self.up_factor
@@ -319,6 +349,8 @@ class SynthesisLayer(torch.nn.Module):
         # host copies of the (constant) FIR taps: the fused kernel takes them by value
         self._fu = None if self.up_filter is None else np.ascontiguousarray(self.up_filter.numpy(), np.float32)
         self._fd = None if self.down_filter is None else np.ascontiguousarray(self.down_filter.numpy(), np.float32)
+        # radial layers: the separable factorisation offered to ic2_flrelu_nhwc_2d (down_rank 0: none, direct kernel)
+        self.down_rank, self._fdv, self._fdh = radial_rank(self._fd) if self.down_radial else (0, None, None)
         self._cache = {}
         self._ig_cache = None
 
@@ -430,11 +462,14 @@ class SynthesisLayer(torch.nn.Module):
         return LayerTrim(border, self.conv_kernel - 1 - border, [p + border * self.up_factor for p in self.padding])
 
     def writes_blocked_output(self, dt):
-        """True when this layer's filtered lrelu has the strip MFMA instance that writes the channel-blocked layout
-        (f16 conv output, up 2 / 4 with 6 * up taps, down 2 with 12 taps)."""
-        return (not self.is_torgb and dt in (torch.bfloat16, torch.float16) and self.up_factor in (2, 4)
-                and self.down_factor == 2 and self._fu is not None and self._fd is not None
-                and self._fu.shape[0] == 6 * self.up_factor and self._fd.shape[0] == 12)
+        """True when this layer's filtered lrelu has an instance that writes the channel-blocked layout: the strip MFMA
+        kernel (f16 conv output, up 2 / 4 with 6 * up taps, down 2 with 12 taps), or on a radial layer the 2-D kernel's
+        16-bit instances (same geometry, 12 x 12 taps)."""
+        if (self.is_torgb or dt not in (torch.bfloat16, torch.float16) or self.up_factor not in (2, 4)
+                or self.down_factor != 2 or self._fu is None or self._fd is None
+                or self._fu.shape != (6 * self.up_factor,)):
+            return False
+        return self._fd.shape == ((12, 12) if self.down_radial else (12,))
 
     def run_nhwc(self, x, n, dt, oscale, post_scale, final_scale=None, x_blocked=False, out_blocked=False, trim=None):
         """x: NHWC [n, in, in, cin_p] (x_blocked: [n, cin_p/16, in, in, 16]) already scaled by this layer's xscale.
@@ -522,6 +557,14 @@ class SynthesisLayer(torch.nn.Module):
         fd = self._fd
         px0, px1, py0, py1 = self.padding if trim is None else trim.flr_padding
         clamp = float(self.conv_clamp) if self.conv_clamp is not None else -1.0
+        if self.down_radial:
+            fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+            nv.call("ic2_flrelu_nhwc16_2d" if blocked else "ic2_flrelu_nhwc_2d", nv.ptr(y), nv.ptr(out),
+                    nv.dtype_code(y.dtype), nv.dtype_code(dt_out) | (nv.flr_out_layout(nv.NHWC16) if out_blocked else 0),
+                    n, self.cout_p, conv, conv, s_out, s_out, fp(fu), 1 if fu is None else fu.shape[0], fp(fd),
+                    fd.shape[0], self.down_rank, fp(self._fdv), fp(self._fdh), None, self.up_factor, self.down_factor,
+                    px0, px1, py0, py1, float(self.act_gain), 0.2, clamp, 0, nv.ptr(post_scale), nv.stream_of(y))
+            return out
         nv.call("ic2_flrelu_nhwc16" if blocked else "ic2_flrelu_nhwc", nv.ptr(y), nv.ptr(out), nv.dtype_code(y.dtype),
                 nv.dtype_code(dt_out) | (nv.flr_out_layout(nv.NHWC16) if out_blocked else 0), n,
                 self.cout_p, conv, conv, s_out, s_out, None if fu is None else fu.ctypes.data_as(ctypes.c_void_p),
@@ -605,6 +648,8 @@ class SynthesisLayer(torch.nn.Module):
         if update_emas:
             raise NotImplementedError("update_emas is a training feature (out of scope)")
         if _train_mode(self, x, w):
+            if self.down_radial:
+                raise nv.AutogradUnsupported(_RADIAL_AUTOGRAD)
             return self.forward_train(x, w)
         x_in, w_in = x, w
         x = x.to(torch.float32).contiguous()
@@ -643,8 +688,15 @@ class SynthesisLayer(torch.nn.Module):
         assert numtaps >= 1
         if numtaps == 1:
             return None
-        if radial:
-            raise NotImplementedError("radial filters (StyleGAN3-R) are not on the path")
+        if radial:  # [SG3-public] jinc low-pass under a separable Kaiser window (numtaps even: r is never 0)
+            x = (np.arange(numtaps) - (numtaps - 1) / 2) / fs
+            r = np.hypot(*np.meshgrid(x, x))
+            f = scipy.special.j1(2 * cutoff * (np.pi * r)) / (np.pi * r)
+            beta = scipy.signal.kaiser_beta(scipy.signal.kaiser_atten(numtaps, width / (fs / 2)))
+            w = np.kaiser(numtaps, beta)
+            f *= np.outer(w, w)
+            f /= np.sum(f)
+            return torch.as_tensor(f, dtype=torch.float32)
         f = scipy.signal.firwin(numtaps=numtaps, cutoff=cutoff, width=width, fs=fs)
         return torch.as_tensor(f, dtype=torch.float32)
 
@@ -714,7 +766,7 @@ class SynthesisNetwork(torch.nn.Module):
         return [getattr(self, name) for name in self.layer_names]
 
     def forward(self, ws, noise_mode="const", force_fp32=False, update_emas=False, **layer_kwargs):
-        """noise_mode is accepted and ignored exactly like SG3 (the T generator has no noise inputs)."""
+        """noise_mode is accepted and ignored exactly like SG3 (the generator has no noise inputs)."""
         assert noise_mode in ("random", "const", "none")
         if update_emas:
             raise NotImplementedError("update_emas is a training feature (out of scope)")
@@ -724,6 +776,8 @@ class SynthesisNetwork(torch.nn.Module):
             # 'f16' trains in f16 only when the caller scales its loss (train_f16: the reference's fp16 autocast +
             # GradScaler, stylegan3_hvae_full.py:487,693-696; unscaled gradients underflow f16), else in bf16
             tdt = dt if dt != torch.float16 or self.train_f16 else torch.bfloat16
+            if any(L.down_radial for L in self.layers()):
+                raise nv.AutogradUnsupported(_RADIAL_AUTOGRAD)
             return self.forward_train(ws, tdt)
         ws_in = ws
         ws = ws.to(torch.float32).contiguous()
@@ -898,7 +952,8 @@ class Generator(torch.nn.Module):
 
 
 def make_generator(img_resolution=256, seed=None, precision="fp32", device="cuda", **kw):
-    """Seeded StyleGAN3-T generator (random init -- no pretrained weights are available offline)."""
+    """Seeded StyleGAN3 generator, T by default, R with **SG3_R_KWARGS (random init -- no pretrained weights are
+    available offline)."""
     if seed is not None:
         torch.manual_seed(seed)
     G = Generator(z_dim=512, c_dim=0, w_dim=512, img_resolution=img_resolution, img_channels=3, precision=precision, **kw)

@@ -179,6 +179,32 @@ int ic2_flrelu_nhwc16(const void* x, void* y, int dtype_in, int dtype_out, int n
                       int up, int down, int px0, int px1, int py0, int py1, float gain, float slope, float clamp,
                       int flip, const float* post_scale, void* stream);
 
+/* ic2_flrelu_nhwc with a NON-SEPARABLE down filter: the StyleGAN3-R configuration, whose non-critical layers low-pass
+ * with a radially symmetric filter (SynthesisLayer's filtered_lrelu with a 2-D fd, SG3-public; the reference hands
+ * whatever generator pickle it is given to G.synthesis, stylegan3_hvae_full.py:274,329).  Same contract as
+ * ic2_flrelu_nhwc (filters in HOST memory, optional bias b, post_scale, IC2_FLR_OUT_LAYOUT bits in dtype_out, every
+ * argument and the output size checked before any launch, IC2_E_UNSUPPORTED with nothing written where no instance
+ * exists), except:
+ *  - fd is fd[fd_taps][fd_taps], row = y, with upfirdn2d's semantics for a 2-D filter: flipped in both axes unless
+ *    `flip`, gain 1.  fu stays the separable 1-D up filter.
+ *  - rank (0 .. 4) with fd_v / fd_h [rank][fd_taps] optionally offers a separable factorisation fd ~ sum_k outer(fd_v[k],
+ *    fd_h[k]) computed by the caller (0: none, fd_v / fd_h ignored).  It is checked, and is a permission only: this
+ *    library has no low-rank instance yet, so every call runs the direct kernel on fd itself (all fd_taps^2 taps, f32
+ *    accumulation).
+ * Instances: up 2 / 4 with 6 * up taps, down 2 with 12 x 12 taps, px0 == py0 (mod up); f32 -> f32, f16 -> f16,
+ * f16 -> bf16, bf16 -> bf16.  ic2_flrelu_nhwc16_2d reads the channel-blocked input [n][c_p/16][in_h][in_w][16]; the
+ * channel-blocked layouts (input and output) are 16-bit only and give the NHWC values bit for bit. */
+int ic2_flrelu_nhwc_2d(const void* x, void* y, int dtype_in, int dtype_out, int n, int c_p, int in_h, int in_w,
+                       int out_h, int out_w, const float* fu, int fu_taps, const float* fd, int fd_taps, int rank,
+                       const float* fd_v, const float* fd_h, const float* b, int up, int down, int px0, int px1,
+                       int py0, int py1, float gain, float slope, float clamp, int flip, const float* post_scale,
+                       void* stream);
+int ic2_flrelu_nhwc16_2d(const void* x, void* y, int dtype_in, int dtype_out, int n, int c_p, int in_h, int in_w,
+                         int out_h, int out_w, const float* fu, int fu_taps, const float* fd, int fd_taps, int rank,
+                         const float* fd_v, const float* fd_h, const float* b, int up, int down, int px0, int px1,
+                         int py0, int py1, float gain, float slope, float clamp, int flip, const float* post_scale,
+                         void* stream);
+
 /* Host only (no GPU): which inputs one axis of the filtered lrelu reads.  The axis has `in` samples, `out` outputs (as
  * the entry points above expect them for this padding), factors up / down, up_taps / down_taps FIR taps (every tap
  * counted as non-zero) and padding (pad_lo, pad_hi), negative = crop.  win[0], win[1]: first and last input index that
