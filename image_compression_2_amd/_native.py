@@ -117,6 +117,9 @@ _SIGS = {
     "ic2_flrelu_bwd_ydot_floats": [_I, _I, _I, _I, _I],
     "ic2_flrelu_bwd_nhwc_ex": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I,
                                _F, _F, _F, _I, _P, _P, _P, _I64, _P],
+    "ic2_flrelu_bwd_2d_ydot_floats": [_I, _I, _I, _I, _I],
+    "ic2_flrelu_bwd_nhwc_2d": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I,
+                               _F, _F, _F, _I, _P, _P, _P, _I64, _P],
     "ic2_scale_bwd_part_floats": [_I, _I, _I],
     "ic2_colsum_div": [_P, _I, _I, _I, _P, _P, _P],
     "ic2_scale_bwd_nhwc": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I64, _P],
@@ -134,7 +137,8 @@ _RESTYPE = {"ic2_conv_plan": ctypes.c_char_p, "ic2_conv_wino_plan": ctypes.c_cha
             "ic2_uint8_sse_scratch_doubles": _I64, "ic2_uint8_quality_scratch_doubles": _I64,
             "ic2_rc_bound": _I64, "ic2_conv_wgrad_ws_floats": _I64,
             "ic2_gn_lrelu_pool_bwd_floats": _I64, "ic2_conv3x3_gn_stats_floats": _I64,
-            "ic2_flrelu_bwd_ydot_floats": _I64, "ic2_scale_bwd_part_floats": _I64,
+            "ic2_flrelu_bwd_ydot_floats": _I64, "ic2_flrelu_bwd_2d_ydot_floats": _I64,
+            "ic2_scale_bwd_part_floats": _I64,
             "ic2_gumbel_softmax_bwd_ws_bytes": _I64}
 
 _lib = None

@@ -349,15 +349,18 @@ def _synth_layer_grads(L, dt, os_, y, dout, post=None):
     # relative error), so dc is stored as is.
     rc = 2
     if fu is not None and fd is not None and px0 == py0:
-        nyd = int(nv.query("ic2_flrelu_bwd_ydot_floats", n, c_p, h, w, L.up_factor))
+        # a radial layer's 2-D down filter [12][12]: the 2-D kernel, with its own ydot tiling
+        fn = "ic2_flrelu_bwd_nhwc_2d" if L.down_radial else "ic2_flrelu_bwd_nhwc_ex"
+        nyd = int(nv.query("ic2_flrelu_bwd_2d_ydot_floats" if L.down_radial else "ic2_flrelu_bwd_ydot_floats", n, c_p,
+                           h, w, L.up_factor))
         ydot = torch.empty([nyd], dtype=torch.float32, device=y.device)
-        rc = nv.load().ic2_flrelu_bwd_nhwc_ex(
+        rc = getattr(nv.load(), fn)(
             nv.ptr(y), nv.dtype_code(y.dtype), nv.ptr(dout), nv.dtype_code(dout.dtype), nv.ptr(dc),
             nv.dtype_code(dt), n, c_p, h, w, dout.shape[1], dout.shape[2], fu.ctypes.data_as(ctypes.c_void_p),
             fu.shape[0], fd.ctypes.data_as(ctypes.c_void_p), fd.shape[0], L.up_factor, L.down_factor, px0, px1,
             py0, py1, float(L.act_gain), 0.2, clamp, 0, nv.ptr(mul), nv.ptr(bp), nv.ptr(ydot), nyd, stream)
         if rc not in (0, 2):
-            raise RuntimeError(f"ic2_flrelu_bwd_nhwc_ex failed: {nv.load().ic2_last_error().decode()}")
+            raise RuntimeError(f"{fn} failed: {nv.load().ic2_last_error().decode()}")
     if rc == 0:   # dL/doscale = sum over tiles of the ydot partials / oscale (0 where oscale is 0), one launch
         d_os = nv.colsum_div(ydot, n, c_p, os32)
         if post is not None:
@@ -517,7 +520,19 @@ class FilteredLReluNHWC(torch.autograd.Function):
         fu, fd = L._fu, L._fd
         px0, px1, py0, py1 = L.padding
         clamp = float(L.conv_clamp) if L.conv_clamp is not None else -1.0
-        if fu is not None and fd is not None and px0 == py0:
+        if L.down_radial and fu is not None and fd is not None and px0 == py0:
+            # the 2-D kernel's (f32, f32, f32) / (f16, f32, f32) instances; other gradient dtypes compose
+            dy = torch.empty([n, h, w, c_p], dtype=torch.float32, device=y.device)
+            rc = nv.load().ic2_flrelu_bwd_nhwc_2d(
+                nv.ptr(y), nv.dtype_code(y.dtype), nv.ptr(dout), nv.dtype_code(dout.dtype), nv.ptr(dy), nv.F32, n, c_p, h,
+                w, dout.shape[1], dout.shape[2], fu.ctypes.data_as(ctypes.c_void_p), fu.shape[0],
+                fd.ctypes.data_as(ctypes.c_void_p), fd.shape[0], L.up_factor, L.down_factor, px0, px1, py0, py1,
+                float(L.act_gain), 0.2, clamp, 0, None, None, None, 0, nv.stream_of(y))
+            if rc == 0:
+                return dy, None, None
+            if rc != 2:
+                raise RuntimeError(f"ic2_flrelu_bwd_nhwc_2d failed: {nv.load().ic2_last_error().decode()}")
+        elif fu is not None and fd is not None and px0 == py0:
             dy = torch.empty([n, h, w, c_p], dtype=torch.float32, device=y.device)
             rc = nv.load().ic2_flrelu_bwd_nhwc(
                 nv.ptr(y), nv.dtype_code(y.dtype), nv.ptr(dout), nv.dtype_code(dout.dtype), nv.ptr(dy), n, c_p, h, w,

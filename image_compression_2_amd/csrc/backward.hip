@@ -717,8 +717,9 @@ extern "C" int ic2_scale_nhwc(const void* x, const float* xscale, void* a, int d
 
 extern "C" int ic2_scale_bwd_nhwc(const void* da, const void* x, const float* xscale, void* dx, int dtype, int n, int hw,
                                   int c_p, float* part, int64_t part_floats, void* stream) {
-  IC2_CHECK_ARG(da && x && xscale && part && n > 0 && hw > 0 && c_p > 0 && c_p % 2 == 0 && c_p <= 512,
+  IC2_CHECK_ARG(da && x && xscale && part && n > 0 && hw > 0 && c_p > 0 && c_p % 2 == 0 && c_p <= 4096,
                 "scale_bwd_nhwc: bad arguments");  // dx may be null: the partial sums only
+  // past 512 channels (StyleGAN3-R: up to 1024) a thread walks several channel pairs; LDS stays PS * c_p floats
   IC2_CHECK_ARG(part_floats >= ic2_scale_bwd_part_floats(n, hw, c_p), "scale_bwd_nhwc: partial buffer too small");
   const int chunk_pix = sb_chunk_pix(n, hw);
   const int nchunks = (int)ceil_div(hw, chunk_pix);

@@ -18,7 +18,8 @@ pickle stores every network as a ``torch_utils.persistence`` record: ``_reconstr
 ``load_network_pkl(f)`` returns ``{'G_ema': Generator, ...}`` (other top-level entries as raw records) so
 ``load_network_pkl(f)['G_ema']`` is the drop-in for the reference line.  The generator is this package's
 ``Generator``, built from the record's ``_init_kwargs`` and filled with ``load_state_dict(strict=True)``.  An SG3-R
-record (``use_radial_filters``) is rejected unless the caller passes ``allow_radial=True``: R runs inference only.
+record (``use_radial_filters``) is rejected unless the caller passes ``allow_radial=True``; training through it needs
+``set_radial_training()``.
 
 Parity: unpinned against a real NVlabs pickle (none is available offline); tests build pickles
 with the same record layout and check the round trip, the allow-list and that injected globals never run.
@@ -187,14 +188,14 @@ def _generator_kwargs(rec, allow_radial=False):
     syn = dict(kw.pop("synthesis_kwargs", {}) or {})
     kw.update(syn)
     if kw.get("use_radial_filters", False) and not allow_radial:
-        raise NotImplementedError("StyleGAN3-R (radial filters) runs inference only (DESIGN.md, StyleGAN3-R): pass "
-                                  "allow_radial=True to load it, or use an SG3-T pickle")
+        raise NotImplementedError("StyleGAN3-R (radial filters; DESIGN.md, StyleGAN3-R): pass allow_radial=True to load "
+                                  "it (training needs set_radial_training()), or use an SG3-T pickle")
     return kw
 
 
 def generator_from_record(rec, precision="fp32", device="cuda", allow_radial=False):
     """Build this package's ``Generator`` from a G/G_ema record and load its weights (strict key match).
-    allow_radial: accept an SG3-R record (radial down filters; inference only)."""
+    allow_radial: accept an SG3-R record (radial down filters; training needs ``set_radial_training()``)."""
     from .networks_stylegan3 import Generator
     if not isinstance(rec, PersistentRecord) or rec.class_name != "Generator":
         raise ValueError(f"expected a persistent Generator record, got {rec!r}")

@@ -1,4 +1,4 @@
-"""MI355X-native StyleGAN3 generator (T, and R for inference): the ``G_ema`` duck type the reference decodes with.
+"""MI355X-native StyleGAN3 generator (T and R): the ``G_ema`` duck type the reference decodes with.
 
 The reference unpickles NVlabs' ``G_ema`` (/root/reference/stylegan3_hvae_full.py:454-455) and calls
 ``G.synthesis(ws, noise_mode=...)`` (``:274, :329``; ``gumbel_softmax_compression.py:193, 262``),
@@ -19,8 +19,10 @@ the filtered lrelu is f16, whose FIR runs on MFMA with f16 operands and fp32 acc
 inference only (the autograd path trains in bf16).  ``precision='fp32'`` (default) is the parity mode (exact-fp32 MFMA).
 
 StyleGAN3-R (``SG3_R_KWARGS``: 1x1 convs, twice the channels, radially symmetric 2-D down filters on the non-critical
-layers) runs the same pipeline for inference, its filtered lrelu through ``ic2_flrelu_nhwc_2d``; its autograd path is
-not implemented and raises ``AutogradUnsupported`` before any launch.
+layers) runs the same pipeline, its filtered lrelu through ``ic2_flrelu_nhwc_2d``.  Its autograd path is opt-in:
+``Generator.set_radial_training()`` switches it on (the filtered lrelu's backward is then ``ic2_flrelu_bwd_nhwc_2d``,
+the 1x1 conv's dgrad the implicit GEMM on the adjoint weights); without the switch an R generator whose input requires
+grad raises ``AutogradUnsupported`` before any launch, so a caller that trains cannot pick one up by accident.
 
 With grad mode on and ``ws`` requiring grad (the reference's encoder training backpropagates through the
 frozen generator, :669-696) ``SynthesisNetwork.forward`` takes the autograd path ``forward_train``: the same
@@ -97,8 +99,9 @@ def _version_key(*tensors):
     return tuple((t.data_ptr(), t._version, t.device) for t in tensors)
 
 
-_RADIAL_AUTOGRAD = ("training through a StyleGAN3-R generator is not implemented: the filtered lrelu has no backward for "
-                    "a 2-D (radial) down filter.  Run it under torch.no_grad() or detach ws / x (inference only)")
+_RADIAL_AUTOGRAD = ("training through a StyleGAN3-R generator is off by default (its filtered lrelu has a 2-D, radial down "
+                    "filter).  Run it under torch.no_grad() or detach ws / x.  Generator.set_radial_training() switches "
+                    "the autograd path on")
 
 
 class LayerTrim:
@@ -333,6 +336,7 @@ class SynthesisLayer(torch.nn.Module):
         assert self.out_sampling_rate * self.down_factor == self.tmp_sampling_rate
         self.down_taps = filter_size * self.down_factor if self.down_factor > 1 and not self.is_torgb else 1
         self.down_radial = bool(use_radial_filters and not self.is_critically_sampled and self.down_taps > 1)
+        self.train_radial = False   # autograd through a radial layer (Generator.set_radial_training)
         self.register_buffer("down_filter", self.design_lowpass_filter(
             numtaps=self.down_taps, cutoff=self.out_cutoff, width=self.out_half_width * 2, fs=self.tmp_sampling_rate,
             radial=self.down_radial))
@@ -648,7 +652,7 @@ class SynthesisLayer(torch.nn.Module):
         if update_emas:
             raise NotImplementedError("update_emas is a training feature (out of scope)")
         if _train_mode(self, x, w):
-            if self.down_radial:
+            if self.down_radial and not self.train_radial:
                 raise nv.AutogradUnsupported(_RADIAL_AUTOGRAD)
             return self.forward_train(x, w)
         x_in, w_in = x, w
@@ -731,6 +735,7 @@ class SynthesisNetwork(torch.nn.Module):
         self.precision = precision
         nv.torch_dtype(precision)
         self.train_f16 = False   # autograd path in f16 (loss-scaled training, training.train_step(scaler=...))
+        self.train_radial = False   # autograd through radial (StyleGAN3-R) layers (Generator.set_radial_training)
 
         last_cutoff = self.img_resolution / 2
         last_stopband = last_cutoff * last_stopband_rel
@@ -776,7 +781,7 @@ class SynthesisNetwork(torch.nn.Module):
             # 'f16' trains in f16 only when the caller scales its loss (train_f16: the reference's fp16 autocast +
             # GradScaler, stylegan3_hvae_full.py:487,693-696; unscaled gradients underflow f16), else in bf16
             tdt = dt if dt != torch.float16 or self.train_f16 else torch.bfloat16
-            if any(L.down_radial for L in self.layers()):
+            if not self.train_radial and any(L.down_radial for L in self.layers()):
                 raise nv.AutogradUnsupported(_RADIAL_AUTOGRAD)
             return self.forward_train(ws, tdt)
         ws_in = ws
@@ -943,6 +948,15 @@ class Generator(torch.nn.Module):
     def set_precision(self, precision):
         nv.torch_dtype(precision)
         self.synthesis.precision = precision
+        return self
+
+    def set_radial_training(self, flag=True):
+        """Opt in to (or out of) the autograd path of a StyleGAN3-R generator: sets ``train_radial`` on the synthesis
+        network and on every layer.  Unset (the default), an R generator whose input requires grad raises
+        ``AutogradUnsupported``.  No effect on a T generator."""
+        self.synthesis.train_radial = bool(flag)
+        for L in self.synthesis.layers():
+            L.train_radial = bool(flag)
         return self
 
     def forward(self, z, c=None, truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs):

@@ -25,6 +25,9 @@ Deviations, all explicit:
     broadcast from rank 0 after each re-creation, so every rank runs -- and averages the gradients of -- the same
     weights (or build the encoder with fix_fine_projector=True: no re-creation at all).
 
+Both steps train through a StyleGAN3-R generator too once ``compressor.generator.set_radial_training()`` was called
+(networks_stylegan3.py; without it an R generator refuses autograd), in fp32, bf16 and loss-scaled f16.
+
 The reference's second trainer, ``train_gumbel_discretized_hvae`` (gumbel_softmax_compression.py:322-611), which also
 trains the quantizer's ``log_temperature`` through the Gumbel-softmax, is ``make_gumbel_optimizer`` +
 ``train_step_gumbel`` below, with the same deviations.

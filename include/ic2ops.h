@@ -514,10 +514,28 @@ int ic2_flrelu_bwd_nhwc_ex(const void* x, int x_dtype, const void* gout, int g_d
                            float gain, float slope, float clamp, int flip, const float* oscale, const float* bias,
                            float* ydot, int64_t ydot_floats, void* stream);
 
+/* ic2_flrelu_bwd_nhwc_ex for a 2-D (radial, non-separable) down filter: the backward of ic2_flrelu_nhwc_2d w.r.t. its
+ * input (training through a StyleGAN3-R generator).  fd: HOST taps [fd_taps][fd_taps], row = y, upfirdn2d semantics
+ * (flipped in both axes unless flip, gain 1).  gV is the polyphase 2-D adjoint (6 x 6 live taps per grid position), the
+ * mask, the separable adjoint up FIR, the oscale store and the ydot partials (taken in f32 before the store is
+ * rounded) are ic2_flrelu_bwd_nhwc_ex's; f32 arithmetic on the stored operands.  Instances: up 2 / 12 taps and up 4 /
+ * 24 taps, down 2 with 12 x 12 taps, px0 == py0, c_p % 16 == 0, (x, gout, gx) = (f32, f32, f32), (f16, bf16, bf16),
+ * (f16, f16, f16: stored IEEE, overflow -> inf for the loss scaler) or (f16, f32, f32); anything else returns
+ * IC2_E_UNSUPPORTED with nothing written (the caller composes ic2_upfirdn2d then).  oscale / bias / ydot nullable.
+ * ydot [n][rows][c_p]: ic2_flrelu_bwd_2d_ydot_floats() floats (its tile differs from ic2_flrelu_bwd_nhwc_ex's), the
+ * layout ic2_colsum_div consumes. */
+int64_t ic2_flrelu_bwd_2d_ydot_floats(int n, int c_p, int in_h, int in_w, int up);
+int ic2_flrelu_bwd_nhwc_2d(const void* x, int x_dtype, const void* gout, int g_dtype, void* gx, int gx_dtype, int n,
+                           int c_p, int in_h, int in_w, int out_h, int out_w, const float* fu, int fu_taps,
+                           const float* fd /* [fd_taps][fd_taps], row = y */, int fd_taps, int up, int down, int px0,
+                           int px1, int py0, int py1, float gain, float slope, float clamp, int flip,
+                           const float* oscale, const float* bias, float* ydot, int64_t ydot_floats, void* stream);
+
 /* Backward of the synthesis input modulation a = x * xscale[n][c] (SG3 modulated_conv2d's style multiply in the
  * activation-scaling form): dx = da * xscale (NHWC, f32 / bf16) and part[n][chunk][c] = per-chunk sums of da * x
  * (dL/dxscale = sum over chunks).  part: ic2_scale_bwd_part_floats() floats.  dx may be NULL (the partial sums only:
- * the training path folds xscale into the FLR backward's per-channel multiplier instead).  Deterministic. */
+ * the training path folds xscale into the FLR backward's per-channel multiplier instead).  Deterministic.
+ * c_p even, at most 4096 (StyleGAN3-R's layers are up to 1024 wide). */
 int64_t ic2_scale_bwd_part_floats(int n, int hw, int c_p);
 int ic2_scale_bwd_nhwc(const void* da, const void* x, const float* xscale, void* dx, int dtype, int n, int hw, int c_p,
                        float* part, int64_t part_floats, void* stream);
