@@ -16,16 +16,14 @@
 //   stage 3  vertical down-FIR : LDS column -> * post_scale -> global
 // Filters are separable 1-D taps (the StyleGAN3-T configuration).  Zero padding / negative
 // padding (crop) is exact: input samples outside [0, L) are zero, as in the reference.
+// Channel-pair access, LDS packing, the activation, the polyphase up-FIR of a grid position (up_fir) and the host
+// side's geometry / tap helpers are flrelu_valu.h's, shared with flrelu_radial.hip and the two backward files.
 #include "flrelu.h"
-
-#include <cmath>
+#include "flrelu_valu.h"
 
 #include <cstdlib>
-#include <type_traits>
 
 namespace ic2 {
-
-typedef float f2v __attribute__((ext_vector_type(2)));
 
 template <int U, int D, int TU, int TD, int TOY, int TOX>
 struct FlrGeom {
@@ -36,17 +34,15 @@ struct FlrGeom {
   static constexpr int NINXP = NINX | 1;               // odd row pitch: conflict-free ds_read_b64
 };
 
-// Branch-free pair access: an out-of-range sample reads the code object's zero line and is then
-// masked, so no load sits behind a branch (hipcc would otherwise wait vmcnt(0) per element).
+// Pair access by layout: channels-last takes the shared vector pair (flrelu_valu.h); NCHW, whose pair sits a channel
+// stride apart, takes two scalar accesses (zero line and masking as there).
 template <typename T, bool CHLAST>
 __device__ __forceinline__ f2v load2(const T* p, int64_t sc, bool ok, bool ok2);
 template <> __device__ __forceinline__ f2v load2<float, true>(const float* p, int64_t, bool ok, bool) {
-  const float2 v = *reinterpret_cast<const float2*>(ok ? (const void*)p : zero_line());
-  return f2v{v.x, v.y};
+  return load_pair<float>(p, ok);
 }
 template <> __device__ __forceinline__ f2v load2<bf16_t, true>(const bf16_t* p, int64_t, bool ok, bool) {
-  const uint32_t v = *reinterpret_cast<const uint32_t*>(ok ? (const void*)p : zero_line());
-  return f2v{__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u)};
+  return load_pair<bf16_t>(p, ok);
 }
 template <> __device__ __forceinline__ f2v load2<float, false>(const float* p, int64_t sc, bool ok, bool ok2) {
   const float a = *reinterpret_cast<const float*>(ok ? (const void*)p : zero_line());
@@ -59,12 +55,8 @@ template <> __device__ __forceinline__ f2v load2<bf16_t, false>(const bf16_t* p,
   return f2v{bf2f(a), bf2f(b)};
 }
 template <typename T, bool CHLAST> __device__ __forceinline__ void store2(T* p, int64_t sc, bool ok2, f2v v);
-template <> __device__ __forceinline__ void store2<float, true>(float* p, int64_t, bool, f2v v) {
-  *reinterpret_cast<float2*>(p) = make_float2(v.x, v.y);
-}
-template <> __device__ __forceinline__ void store2<bf16_t, true>(bf16_t* p, int64_t, bool, f2v v) {
-  *reinterpret_cast<uint32_t*>(p) = (uint32_t)f2bf(v.x) | ((uint32_t)f2bf(v.y) << 16);
-}
+template <> __device__ __forceinline__ void store2<float, true>(float* p, int64_t, bool, f2v v) { store_pair(p, v); }
+template <> __device__ __forceinline__ void store2<bf16_t, true>(bf16_t* p, int64_t, bool, f2v v) { store_pair(p, v); }
 template <> __device__ __forceinline__ void store2<float, false>(float* p, int64_t sc, bool ok2, f2v v) {
   p[0] = v.x;
   if (ok2) p[sc] = v.y;
@@ -74,40 +66,7 @@ template <> __device__ __forceinline__ void store2<bf16_t, false>(bf16_t* p, int
   if (ok2) p[sc] = f2bf(v.y);
 }
 
-// LDS storage of the up-sampled grid: fp32 pairs (parity path) or packed bf16 pairs (bf16 path:
-// halves the LDS footprint -> twice the resident workgroups; one extra rounding of the vertically
-// up-sampled input, below the bf16 rounding of the output itself).
-template <typename LT> struct LdsPair;
-template <> struct LdsPair<f2v> {
-  __device__ static __forceinline__ f2v pack(f2v v) { return v; }
-  __device__ static __forceinline__ f2v unpack(f2v v) { return v; }
-};
-template <> struct LdsPair<uint32_t> {
-  __device__ static __forceinline__ uint32_t pack(f2v v) { return (uint32_t)f2bf(v.x) | ((uint32_t)f2bf(v.y) << 16); }
-  __device__ static __forceinline__ f2v unpack(uint32_t v) {
-    return f2v{__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u)};
-  }
-};
-
-// lrelu + clamp on a channel pair in 5 instructions: one packed multiply, two max (slope <= 1 makes
-// lrelu(v) = max(v, slope*v)) and two med3 clamps.  The gain is folded into the horizontal down taps
-// and the clamp bound divided by it: clamp(gain*lrelu(v), +-c) = gain * clamp(lrelu(v), +-c/gain).
-__device__ __forceinline__ f2v act2(f2v v, float slope, float lim) {
-  const f2v sv = v * slope;
-  f2v r;
-  r.x = __builtin_amdgcn_fmed3f(fmaxf(v.x, sv.x), -lim, lim);
-  r.y = __builtin_amdgcn_fmed3f(fmaxf(v.y, sv.y), -lim, lim);
-  return r;
-}
-
 constexpr int FLR_S3 = 4;                // stage-3 row split (items = columns x pairs x FLR_S3)
-
-// First input sample j whose up-FIR tap t = U*j + DELTA - i lies in [0, TU): j = ceil((i - DELTA) / U),
-// clamped at 0.  The TU/U samples j, j+1, ... are exactly the polyphase taps of grid position i.
-template <int U, int DELTA>
-__host__ __device__ constexpr int up_first(int i) {
-  return i < DELTA ? 0 : (i - DELTA + U - 1) / U;
-}
 
 template <typename TI, typename TO, bool CHLAST, int U, int D, int TU, int TD, int DELTA, int TOY, int TOX, int FLR_CPB,
           int FLR_THREADS>
@@ -121,13 +80,8 @@ __global__ void __launch_bounds__(FLR_THREADS) __attribute__((amdgpu_waves_per_e
   constexpr int NCG = FLR_NCG;
   __shared__ __attribute__((aligned(16))) LT buf[RAY * NINXP * NCG];
 
-  int bid = blockIdx.x;
-  const int cb = bid % a.cblocks;
-  bid /= a.cblocks;
-  const int tx = bid % a.tiles_x;
-  bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int n = bid / a.tiles_y;
+  const FlrBlock blk = flr_block(a);
+  const int cb = blk.cb, tx = blk.tx, ty = blk.ty, n = blk.n;
 
   const int oy0 = ty * TOY, ox0 = tx * TOX;
   // first input sample feeding the tile: s_lo = (ka - p0 + DELTA) / U with ka = o0 * D
@@ -161,15 +115,8 @@ __global__ void __launch_bounds__(FLR_THREADS) __attribute__((amdgpu_waves_per_e
       in[j] = ok ? v : f2v{0.f, 0.f};
     }
 #pragma unroll
-    for (int i = 0; i < RAY; ++i) {
-      f2v acc = f2v{0.f, 0.f};
-#pragma unroll
-      for (int m = 0; m < TU / U; ++m) {  // the TU/U polyphase taps landing on grid row i
-        const int j = up_first<U, DELTA>(i) + m;
-        if (j < NINY) acc += a.gu[U * j + DELTA - i] * in[j];
-      }
-      buf[(i * NINXP + xs) * NCG + cg] = LP::pack(acc);
-    }
+    for (int i = 0; i < RAY; ++i)
+      buf[(i * NINXP + xs) * NCG + cg] = LP::pack(up_fir<U, TU, DELTA, NINY>(a.gu, i, in));
   }
   __syncthreads();
 
@@ -185,13 +132,7 @@ __global__ void __launch_bounds__(FLR_THREADS) __attribute__((amdgpu_waves_per_e
     for (int o = 0; o < TOX; ++o) d[o] = f2v{0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < RAX; ++k) {
-      f2v v = f2v{0.f, 0.f};
-#pragma unroll
-      for (int m = 0; m < TU / U; ++m) {
-        const int j = up_first<U, DELTA>(k) + m;
-        if (j < NINX) v += a.gu[U * j + DELTA - k] * in[j];
-      }
-      v = act2(v, a.slope, a.lim);
+      const f2v v = act2(up_fir<U, TU, DELTA, NINX>(a.gu, k, in), a.slope, a.lim);
 #pragma unroll
       for (int m = 0; m < TD / D; ++m) {  // outputs o with 0 <= k - o*D < TD
         const int o = k / D - m;
@@ -329,9 +270,10 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
   const bool out_blocked = out_layout == IC2_LAYOUT_NHWC16;
   IC2_CHECK_ARG(n > 0 && c > 0 && in_h > 0 && in_w > 0 && up >= 1 && down >= 1, "%s: bad geometry", name);
   IC2_CHECK_ARG(fu_taps >= 1 && fd_taps >= 1 && fu_taps <= 24 && fd_taps <= 12, "%s: unsupported taps", name);
-  const int ew = (in_w * up + (px0 + px1) - (fu_taps - 1) - (fd_taps - 1) + (down - 1)) / down;
-  const int eh = (in_h * up + (py0 + py1) - (fu_taps - 1) - (fd_taps - 1) + (down - 1)) / down;
-  IC2_CHECK_ARG(out_h == eh && out_w == ew, "%s: output %dx%d, expected %dx%d", name, out_h, out_w, eh, ew);
+  const int64_t ew = flr_out_size(in_w, up, px0, px1, fu_taps, fd_taps, down);
+  const int64_t eh = flr_out_size(in_h, up, py0, py1, fu_taps, fd_taps, down);
+  IC2_CHECK_ARG(out_h == eh && out_w == ew, "%s: output %dx%d, expected %lldx%lld", name, out_h, out_w, (long long)eh,
+                (long long)ew);
   IC2_CHECK_ARG(out_h > 0 && out_w > 0, "%s: empty output", name);
   // one polyphase offset serves both axes -> needs px0 == py0 (mod up); the fused instances exist for
   // the StyleGAN3-T configurations only
@@ -340,7 +282,7 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
     set_error("%s: px0 and py0 differ mod up", name);
     return IC2_E_UNSUPPORTED;
   }
-  if (!(slope >= 0.f && slope <= 1.f && gain > 0.f)) {  // the fused activation uses max(v, slope*v)
+  if (!flr_act_ok(slope, gain)) {
     set_error("%s: fused path needs 0 <= slope <= 1 and gain > 0", name);
     return IC2_E_UNSUPPORTED;
   }
@@ -372,18 +314,19 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
                        (dtype_out == IC2_BF16 || dtype_out == IC2_F16) && b == nullptr && dx == dy;
   a.out_f16 = dtype_out == IC2_F16;
   a.out_blocked = out_blocked;
+  a.slope = slope;
+  a.lim = flr_lim(clamp, gain);
+  // the exact taps, once for both formulations: the VALU kernel takes them as they are, the MFMA kernels rounded
+  float gu[24], gd[12], gdg[12];
+  flr_up_taps(gu, fu, fu_taps, up, flip);
+  flr_down_taps(gd, fd, fd_taps, flip);
+  for (int t = 0; t < 12; ++t) gdg[t] = gd[t] * gain;
   if ((use_mfma || dtype_in == IC2_F16) && mfma_ok) {
-    float gu[24] = {}, gd[12] = {}, gdg[12] = {};
-    for (int t = 0; t < fu_taps; ++t) gu[t] = (fu ? (flip ? fu[t] : fu[fu_taps - 1 - t]) : 1.f) * (float)up;
-    for (int t = 0; t < fd_taps; ++t) gd[t] = fd ? (flip ? fd[t] : fd[fd_taps - 1 - t]) : 1.f;
-    for (int t = 0; t < fd_taps; ++t) gdg[t] = gd[t] * gain;
     for (int t = 0; t < 24; ++t) a.gu[t] = 0.f;
     for (int t = 0; t < 12; ++t) a.gd[t] = a.gdg[t] = 0.f;
     f16_round_taps(gu, a.gu, fu_taps, up);  // one group per polyphase phase (fu_taps = 6 * up)
     f16_round_taps(gd, a.gd, fd_taps, 1);
     f16_round_taps(gdg, a.gdg, fd_taps, 1);
-    a.slope = slope;
-    a.lim = clamp >= 0.f ? clamp / gain : INFINITY;
     for (int t = 0; t < 24; ++t) a.guh[t] = 0.f;
     for (int t = 0; t < 12; ++t) a.gdgl[t] = 0.f;
     if (clamp >= 0.f) {  // the clamp-split kernels' horizontal passes: u / lim and the gain * lim down taps
@@ -418,14 +361,9 @@ static int flrelu_common(const void* x, void* y, int dtype_in, int dtype_out, bo
   a.tiles_y = (int)ceil_div(out_h, fv.toy);
   a.cblocks = (int)ceil_div(a.c, fv.cpb);
   a.nimg = n;
-  a.slope = slope;
-  a.lim = clamp >= 0.f ? clamp / gain : INFINITY;
-  for (int t = 0; t < 24; ++t) a.gu[t] = 0.f;
-  for (int t = 0; t < 12; ++t) a.gd[t] = 0.f;
-  // NOTE: fu / fd are HOST pointers here (filters are layer constants; they travel in the kernarg)
-  for (int t = 0; t < fu_taps; ++t) a.gu[t] = (fu ? (flip ? fu[t] : fu[fu_taps - 1 - t]) : 1.f) * (float)up;
-  for (int t = 0; t < fd_taps; ++t) a.gd[t] = fd ? (flip ? fd[t] : fd[fd_taps - 1 - t]) : 1.f;
-  for (int t = 0; t < 12; ++t) a.gdg[t] = a.gd[t] * gain;
+  for (int t = 0; t < 24; ++t) a.gu[t] = gu[t];
+  for (int t = 0; t < 12; ++t) a.gd[t] = gd[t];
+  for (int t = 0; t < 12; ++t) a.gdg[t] = gdg[t];
   const int64_t grid = (int64_t)n * a.tiles_y * a.tiles_x * a.cblocks;
   IC2_CHECK_ARG(grid < (1LL << 31), "%s: grid too large", name);
   int rc;

@@ -19,8 +19,12 @@
 //            down-by-up FIR -> written back over the thread's own a_v row
 //   stage C  per column: vertical down-by-up FIR -> gx (f32) -> global
 // f32 arithmetic throughout (the gradient is returned in f32 whatever the forward's storage dtype).
+// Shared with flrelu_radial_bwd.hip through flrelu_valu.h: the pair access and act' (dact), the up-FIR rows of stage A
+// (bwd_up_rows), the adjoint up-FIR scatter of stages B and C (up_adjoint) and stage C itself (bwd_stage_c; this file
+// passes the store on its run-time out_bf16 flag).
 #include "common.h"
 #include "flrelu.h"
+#include "flrelu_valu.h"
 
 #include <cstdlib>
 
@@ -30,9 +34,6 @@ int flrelu_bwd_mfma_launch(const void* x, const void* gout, void* gx, const floa
                            float* ydot, int64_t ydot_floats, int n, int c_p, int in_h, int in_w, int out_h, int out_w,
                            const float* gu, const float* gd, int up, int p0, float gain, float slope, float lim,
                            bool grad_f16, hipStream_t s);
-
-typedef float bf2v __attribute__((ext_vector_type(2)));
-typedef _Float16 hh2v __attribute__((ext_vector_type(2)));
 
 struct FlrBwdArgs {
   const void* x;     // conv output that fed the forward (NHWC [n][in_h][in_w][c_p], f32 or f16)
@@ -51,26 +52,6 @@ struct FlrBwdArgs {
   float gd[12];
 };
 
-template <typename T> __device__ __forceinline__ bf2v ldp(const T* p, bool ok);
-template <> __device__ __forceinline__ bf2v ldp<float>(const float* p, bool ok) {
-  const float2 v = *reinterpret_cast<const float2*>(ok ? (const void*)p : zero_line());
-  return bf2v{v.x, v.y};
-}
-template <> __device__ __forceinline__ bf2v ldp<_Float16>(const _Float16* p, bool ok) {
-  const uint32_t u = *reinterpret_cast<const uint32_t*>(ok ? (const void*)p : zero_line());
-  const hh2v h = __builtin_bit_cast(hh2v, u);
-  return bf2v{(float)h.x, (float)h.y};
-}
-template <> __device__ __forceinline__ bf2v ldp<bf16_t>(const bf16_t* p, bool ok) {
-  const uint32_t u = *reinterpret_cast<const uint32_t*>(ok ? (const void*)p : zero_line());
-  return bf2v{__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)};
-}
-
-__device__ __forceinline__ float dact(float u, float slope, float gain, float lim) {
-  const float l = u > 0.f ? u : u * slope;
-  return fabsf(l) < lim ? (u > 0.f ? gain : gain * slope) : 0.f;
-}
-
 template <int UP, int DN, int TU, int TD, int TIY, int TIX>
 struct FbGeom {
   static constexpr int KY = (TIY - 1) * UP + TU;   // lrelu-grid rows feeding the tile
@@ -87,16 +68,11 @@ __global__ void __launch_bounds__(NT) flrelu_bwd_kernel(FlrBwdArgs a) {
   constexpr int NOY = (R + KY - 1) / DN + 1;  // gout rows / columns feeding the grid rows
   constexpr int NOX = (R + KX - 1) / DN + 1;
   constexpr int PA = NJX | 1, PB = NOX | 1;   // odd row pitches
-  __shared__ __attribute__((aligned(16))) bf2v a_v[KY * PA * NP];
-  __shared__ __attribute__((aligned(16))) bf2v b_v[KY * PB * NP];
+  __shared__ __attribute__((aligned(16))) f2v a_v[KY * PA * NP];
+  __shared__ __attribute__((aligned(16))) f2v b_v[KY * PB * NP];
 
-  int bid = blockIdx.x;
-  const int cb = bid % a.cblocks;
-  bid /= a.cblocks;
-  const int tx = bid % a.tiles_x;
-  bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int n = bid / a.tiles_y;
+  const FlrBlock blk = flr_block(a);
+  const int cb = blk.cb, tx = blk.tx, ty = blk.ty, n = blk.n;
   const int i0y = ty * TIY, i0x = tx * TIX;
   const int j0y = i0y - TU / UP + 1, j0x = i0x - TU / UP + 1;
   // first gout row / column: (k0 - td + 1 + ph) / down, exact (R = td - 1 - ph)
@@ -115,41 +91,31 @@ __global__ void __launch_bounds__(NT) flrelu_bwd_kernel(FlrBwdArgs a) {
       const int ix = j0x + col;
       const bool cok = (unsigned)ix < (unsigned)a.in_w;
       const TI* pc = xin + (int64_t)ix * a.c_p + c;
-      bf2v in[NJY];
+      f2v in[NJY];
 #pragma unroll
       for (int j = 0; j < NJY; ++j) {
         const int iy = j0y + j;
         const bool ok = cok && (unsigned)iy < (unsigned)a.in_h;
-        const bf2v v = ldp<TI>(pc + (int64_t)iy * a.in_w * a.c_p, ok);
-        in[j] = ok ? v : bf2v{0.f, 0.f};
+        const f2v v = load_pair<TI>(pc + (int64_t)iy * a.in_w * a.c_p, ok);
+        in[j] = ok ? v : f2v{0.f, 0.f};
       }
-#pragma unroll
-      for (int k = 0; k < KY; ++k) {
-        bf2v acc = bf2v{0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < TU / UP; ++m) {
-          const int j = k / UP + m;
-          const int t = (j + 1) * UP - 1 - k;
-          if (j < NJY && t >= 0 && t < TU) acc += a.gu[t] * in[j];
-        }
-        a_v[(k * PA + col) * NP + p] = acc;
-      }
+      bwd_up_rows<UP, TU, KY, NJY>(a.gu, in, a_v + col * NP + p, PA * NP);
     } else {
       const int oc = col - NJX;
       const int ox = o0x + oc;
       const bool cok = (unsigned)ox < (unsigned)a.out_w;
       const TG* pc = gin + (int64_t)ox * a.c_p + c;
-      bf2v in[NOY];
+      f2v in[NOY];
 #pragma unroll
       for (int o = 0; o < NOY; ++o) {
         const int oy = o0y + o;
         const bool ok = cok && (unsigned)oy < (unsigned)a.out_h;
-        const bf2v v = ldp<TG>(pc + (int64_t)oy * a.out_w * a.c_p, ok);
-        in[o] = ok ? v : bf2v{0.f, 0.f};
+        const f2v v = load_pair<TG>(pc + (int64_t)oy * a.out_w * a.c_p, ok);
+        in[o] = ok ? v : f2v{0.f, 0.f};
       }
 #pragma unroll
       for (int k = 0; k < KY; ++k) {
-        bf2v acc = bf2v{0.f, 0.f};
+        f2v acc = f2v{0.f, 0.f};
 #pragma unroll
         for (int m = 0; m < TD / DN; ++m) {
           const int o = (R + k) / DN - m;
@@ -166,16 +132,16 @@ __global__ void __launch_bounds__(NT) flrelu_bwd_kernel(FlrBwdArgs a) {
   for (int item = threadIdx.x; item < KY * NP; item += NT) {
     const int k = item / NP;
     const int p = item - k * NP;
-    bf2v ua[NJX], gb[NOX], ch[TIX];
+    f2v ua[NJX], gb[NOX], ch[TIX];
 #pragma unroll
     for (int j = 0; j < NJX; ++j) ua[j] = a_v[(k * PA + j) * NP + p];
 #pragma unroll
     for (int o = 0; o < NOX; ++o) gb[o] = b_v[(k * PB + o) * NP + p];
 #pragma unroll
-    for (int i = 0; i < TIX; ++i) ch[i] = bf2v{0.f, 0.f};
+    for (int i = 0; i < TIX; ++i) ch[i] = f2v{0.f, 0.f};
 #pragma unroll
     for (int kx = 0; kx < KX; ++kx) {
-      bf2v u = bf2v{0.f, 0.f}, g = bf2v{0.f, 0.f};
+      f2v u = f2v{0.f, 0.f}, g = f2v{0.f, 0.f};
 #pragma unroll
       for (int m = 0; m < TU / UP; ++m) {
         const int j = kx / UP + m;
@@ -190,94 +156,22 @@ __global__ void __launch_bounds__(NT) flrelu_bwd_kernel(FlrBwdArgs a) {
       }
       g.x *= dact(u.x, a.slope, a.gain, a.lim);
       g.y *= dact(u.y, a.slope, a.gain, a.lim);
-#pragma unroll
-      for (int m = 0; m < TU / UP; ++m) {  // outputs i with 0 <= i*UP + TU - 1 - kx < TU
-        const int i = (kx - TU + UP + UP * TU) / UP - TU + m;  // ceil((kx - TU + 1) / UP) + m, kept >= 0 inside
-        const int t = i * UP + TU - 1 - kx;
-        if (i >= 0 && i < TIX && t >= 0 && t < TU) ch[i] += a.gu[t] * g;
-      }
+      up_adjoint<UP, TU, TIX>(a.gu, kx, g, ch);
     }
 #pragma unroll
     for (int i = 0; i < TIX; ++i) a_v[(k * PA + i) * NP + p] = ch[i];
   }
   __syncthreads();
 
-  // ---------------- stage C: vertical down-by-up pass per column, store
-  // Optional epilogue (the modulated conv's backward, x = conv * oscale + bias): gx * oscale is stored (bf16 for
-  // the dgrad GEMM), and sum gx * (x - bias) over the tile goes to ydot -> d oscale = sum / oscale on the host.
-  constexpr int S3 = (TIY % 2 == 0 && TIX * NP * 2 <= NT) ? 2 : 1;
-  constexpr int RG = TIY / S3;
-  constexpr int RGK = (RG - 1) * UP + TU;
-  constexpr int NITEM = TIX * NP * S3;
-  static_assert(NITEM <= NT, "stage C: one item per thread");
-  bf2v ydp = bf2v{0.f, 0.f};
-  const int item = threadIdx.x;
-  const int p = item % NP;
-  const int c = c0 + 2 * p;
-  if (item < NITEM) {
-    const int ix = (item / NP) % TIX;
-    const int rg = item / (NP * TIX);
-    const int gxx = i0x + ix;
-    if (gxx < a.in_w) {
-      bf2v o[RG];
-#pragma unroll
-      for (int r = 0; r < RG; ++r) o[r] = bf2v{0.f, 0.f};
-      const int kb = rg * RG * UP;
-#pragma unroll
-      for (int kk = 0; kk < RGK; ++kk) {
-        const bf2v v = a_v[((kb + kk) * PA + ix) * NP + p];
-#pragma unroll
-        for (int m = 0; m < TU / UP; ++m) {
-          const int r = (kk - TU + UP + UP * TU) / UP - TU + m;
-          const int t = r * UP + TU - 1 - kk;
-          if (r >= 0 && r < RG && t >= 0 && t < TU) o[r] += a.gu[t] * v;
-        }
-      }
-      bf2v os = bf2v{1.f, 1.f}, bi = bf2v{0.f, 0.f};
-      if (a.oscale) os = bf2v{a.oscale[(int64_t)n * a.c_p + c], a.oscale[(int64_t)n * a.c_p + c + 1]};
-      if (a.bias) bi = bf2v{a.bias[c], a.bias[c + 1]};
-      // the ydot operand x of every row BEFORE the first gx store: a load placed after a store to gx may alias
-      // it, which serialised one round trip per row (vmcnt(0) per row in the up-4 instances)
-      if (a.ydot) {
-        bf2v xv[RG];
-#pragma unroll
-        for (int r = 0; r < RG; ++r) {
-          const int gyy = i0y + rg * RG + r;
-          xv[r] = ldp<TI>(xin + ((int64_t)gyy * a.in_w + gxx) * a.c_p + c, gyy < a.in_h);
-        }
-#pragma unroll
-        for (int r = 0; r < RG; ++r)
-          if (i0y + rg * RG + r < a.in_h) ydp += o[r] * (xv[r] - bi);
-      }
-#pragma unroll
-      for (int r = 0; r < RG; ++r) {
-        const int gyy = i0y + rg * RG + r;
-        if (gyy >= a.in_h) continue;
-        const int64_t e = ((int64_t)gyy * a.in_w + gxx) * a.c_p + c;
-        const bf2v v = o[r] * os;
-        if (a.out_bf16) {
-          bf16_t* po = reinterpret_cast<bf16_t*>(a.gx) + (int64_t)n * a.in_h * a.in_w * a.c_p + e;
-          *reinterpret_cast<uint32_t*>(po) = (uint32_t)f2bf(v.x) | ((uint32_t)f2bf(v.y) << 16);
-        } else {
-          float* po = reinterpret_cast<float*>(a.gx) + (int64_t)n * a.in_h * a.in_w * a.c_p + e;
-          *reinterpret_cast<float2*>(po) = make_float2(v.x, v.y);
-        }
-      }
-    }
-  }
-  if (a.ydot) {  // fixed-order reduction of the tile's items per channel pair (LDS reused after a barrier)
-    __syncthreads();
-    if (item < NITEM) a_v[item] = ydp;
-    __syncthreads();
-    if (item < NP) {
-      bf2v t = bf2v{0.f, 0.f};
-      for (int k = item; k < NITEM; k += NP) t += a_v[k];
-      const int tile = ty * a.tiles_x + tx;
-      float* py = a.ydot + ((int64_t)n * a.tiles_y * a.tiles_x + tile) * a.c_p + c;
-      py[0] = t.x;
-      py[1] = t.y;
-    }
-  }
+  // ---------------- stage C: vertical down-by-up pass per column, store, ydot (flrelu_valu.h)
+  // (the store captures by value what it reads, for the reason given at bwd_stage_c)
+  const int64_t gxn = (int64_t)n * a.in_h * a.in_w * a.c_p;
+  void* const gx = a.gx;
+  const bool out_bf16 = a.out_bf16;
+  bwd_stage_c<TI, UP, TU, KY, TIY, TIX, PA, NP, NT>(a, xin, a_v, blk, c0, [=](int64_t e, f2v v) {
+    if (out_bf16) store_pair(reinterpret_cast<bf16_t*>(gx) + gxn + e, v);
+    else store_pair(reinterpret_cast<float*>(gx) + gxn + e, v);
+  });
 }
 
 template <int UP, int DN, int TU, int TD, int R, int TIY, int TIX, int NP, int NT>
@@ -318,12 +212,12 @@ extern "C" int ic2_flrelu_bwd_nhwc_ex(const void* x, int x_dtype, const void* go
   IC2_CHECK_ARG(x_dtype == IC2_F32 || x_dtype == IC2_F16, "flrelu_bwd_nhwc: x must be f32 or f16");
   IC2_CHECK_ARG(g_dtype == IC2_F32 || g_dtype == IC2_BF16 || g_dtype == IC2_F16,
                 "flrelu_bwd_nhwc: gout must be f32, bf16 or f16");
-  const int ew = (in_w * up + (px0 + px1) - (fu_taps - 1) - (fd_taps - 1) + (down - 1)) / down;
-  const int eh = (in_h * up + (py0 + py1) - (fu_taps - 1) - (fd_taps - 1) + (down - 1)) / down;
-  IC2_CHECK_ARG(out_h == eh && out_w == ew && out_h > 0, "flrelu_bwd_nhwc: output %dx%d, expected %dx%d", out_h, out_w,
-                eh, ew);
+  const int64_t ew = flr_out_size(in_w, up, px0, px1, fu_taps, fd_taps, down);
+  const int64_t eh = flr_out_size(in_h, up, py0, py1, fu_taps, fd_taps, down);
+  IC2_CHECK_ARG(out_h == eh && out_w == ew && out_h > 0, "flrelu_bwd_nhwc: output %dx%d, expected %lldx%lld", out_h,
+                out_w, (long long)eh, (long long)ew);
   IC2_CHECK_ARG(px0 == py0, "flrelu_bwd_nhwc: needs px0 == py0");
-  IC2_CHECK_ARG(slope >= 0.f && slope <= 1.f && gain > 0.f, "flrelu_bwd_nhwc: needs 0 <= slope <= 1, gain > 0");
+  IC2_CHECK_ARG(flr_act_ok(slope, gain), "flrelu_bwd_nhwc: needs 0 <= slope <= 1, gain > 0");
   const bool cfg2 = up == 2 && down == 2 && fu_taps == 12 && fd_taps == 12;
   const bool cfg4 = up == 4 && down == 2 && fu_taps == 24 && fd_taps == 12;
   if (!cfg2 && !cfg4) {
@@ -340,11 +234,9 @@ extern "C" int ic2_flrelu_bwd_nhwc_ex(const void* x, int x_dtype, const void* go
   a.x = x; a.gout = gout; a.gx = gx;
   a.oscale = oscale; a.bias = bias; a.ydot = ydot; a.out_bf16 = gx_dtype == IC2_BF16;
   a.c_p = c_p; a.in_h = in_h; a.in_w = in_w; a.out_h = out_h; a.out_w = out_w; a.p0 = px0;
-  a.slope = slope; a.gain = gain; a.lim = clamp >= 0.f ? clamp / gain : INFINITY;
-  for (int t = 0; t < 24; ++t) a.gu[t] = 0.f;
-  for (int t = 0; t < 12; ++t) a.gd[t] = 0.f;
-  for (int t = 0; t < fu_taps; ++t) a.gu[t] = (flip ? fu[t] : fu[fu_taps - 1 - t]) * (float)up;
-  for (int t = 0; t < fd_taps; ++t) a.gd[t] = flip ? fd[t] : fd[fd_taps - 1 - t];
+  a.slope = slope; a.gain = gain; a.lim = flr_lim(clamp, gain);
+  flr_up_taps(a.gu, fu, fu_taps, up, flip);
+  flr_down_taps(a.gd, fd, fd_taps, flip);
   // the bf16 training path (f16 x, bf16 gout and gx): the MFMA kernel (flrelu_bwd_mfma.hip) unless knob
   // IC2_FLRB_MFMA=0; ydot from the stored gx there
   static const bool mfma = knob("IC2_FLRB_MFMA", 1) != 0;
@@ -368,10 +260,7 @@ extern "C" int ic2_flrelu_bwd_nhwc_ex(const void* x, int x_dtype, const void* go
     }
     if (rc != IC2_E_UNSUPPORTED || gf16) return rc;
   }
-  // gout phase: R = td - 1 - ph with ph = (-(p0 - tu + 1 - td + 1)) mod down (up % down == 0: same for every tile)
-  const int q = px0 - fu_taps + 1 - fd_taps + 1;
-  const int ph = ((-q) % down + down) % down;
-  const int R = fd_taps - 1 - ph;
+  const int R = flr_gout_phase(px0, fu_taps, fd_taps, down);
   const int np = cfg2 ? 2 : 1;  // channel pairs per workgroup
   a.tiles_x = (int)ceil_div(in_w, FB_TILE);
   a.tiles_y = (int)ceil_div(in_h, FB_TILE);

@@ -10,18 +10,14 @@
 //   stage 2  horizontal up-FIR : LDS row (registers) -> lrelu, clamp -> written back over the thread's own row, even and
 //                                odd grid columns in separate planes (stage 3 then reads consecutive addresses)
 //   stage 3  all 12 x 12 down taps per output, RY output rows of one column per lane -> * post_scale -> global
-// The polyphase up-FIR indexing and the zero padding / crop are those of flrelu.hip.  Input NHWC or channel-blocked
+// The polyphase up-FIR (up_fir), the pair access, the LDS packing, the activation and the host helpers are
+// flrelu_valu.h's, shared with flrelu.hip; the zero padding / crop is handled as there.  Input NHWC or channel-blocked
 // NHWC16, output NHWC or NHWC16: the layouts differ in strides only, so they give the same bits.
 #include "flrelu.h"
-
-#include <cmath>
-#include <type_traits>
+#include "flrelu_valu.h"
 
 namespace ic2 {
 namespace {
-
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 
 constexpr int R2_D = 2, R2_TD = 12;  // the instances: down 2 with a 12 x 12 filter
 constexpr int R2_NCG = 8;            // channel pairs per workgroup (16 channels)
@@ -43,57 +39,6 @@ struct Flr2dArgs {
   float gd[R2_TD * R2_TD];      // down taps [tx][ty] (transposed: stage 3 walks ty), flipped unless flip_filter, times gain
 };
 
-template <typename T> __device__ __forceinline__ f2v load_pair(const T* p, bool ok);
-template <> __device__ __forceinline__ f2v load_pair<float>(const float* p, bool ok) {
-  const float2 v = *reinterpret_cast<const float2*>(ok ? (const void*)p : zero_line());
-  return f2v{v.x, v.y};
-}
-template <> __device__ __forceinline__ f2v load_pair<bf16_t>(const bf16_t* p, bool ok) {
-  const uint32_t v = *reinterpret_cast<const uint32_t*>(ok ? (const void*)p : zero_line());
-  return f2v{__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u)};
-}
-template <> __device__ __forceinline__ f2v load_pair<_Float16>(const _Float16* p, bool ok) {
-  const h2v v = *reinterpret_cast<const h2v*>(ok ? (const void*)p : zero_line());
-  return f2v{(float)v.x, (float)v.y};
-}
-template <typename T> __device__ __forceinline__ void store_pair(T* p, f2v v);
-template <> __device__ __forceinline__ void store_pair<float>(float* p, f2v v) {
-  *reinterpret_cast<float2*>(p) = make_float2(v.x, v.y);
-}
-template <> __device__ __forceinline__ void store_pair<bf16_t>(bf16_t* p, f2v v) {
-  *reinterpret_cast<uint32_t*>(p) = (uint32_t)f2bf(v.x) | ((uint32_t)f2bf(v.y) << 16);
-}
-template <> __device__ __forceinline__ void store_pair<_Float16>(_Float16* p, f2v v) {  // saturating, as Elem<_Float16>
-  *reinterpret_cast<h2v*>(p) = h2v{(_Float16)__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f),
-                                   (_Float16)__builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f)};
-}
-
-template <typename LT> struct Lds2;
-template <> struct Lds2<f2v> {
-  __device__ static __forceinline__ f2v pack(f2v v) { return v; }
-  __device__ static __forceinline__ f2v unpack(f2v v) { return v; }
-};
-template <> struct Lds2<h2v> {  // saturating: the vertically up-sampled input may pass the f16 range by the filter's overshoot
-  __device__ static __forceinline__ h2v pack(f2v v) {
-    return h2v{(_Float16)__builtin_amdgcn_fmed3f(v.x, -65504.f, 65504.f),
-               (_Float16)__builtin_amdgcn_fmed3f(v.y, -65504.f, 65504.f)};
-  }
-  __device__ static __forceinline__ f2v unpack(h2v v) { return f2v{(float)v.x, (float)v.y}; }
-};
-
-__device__ __forceinline__ f2v act_pair(f2v v, float slope, float lim) {  // slope <= 1: lrelu(v) = max(v, slope * v)
-  const f2v sv = v * slope;
-  f2v r;
-  r.x = __builtin_amdgcn_fmed3f(fmaxf(v.x, sv.x), -lim, lim);
-  r.y = __builtin_amdgcn_fmed3f(fmaxf(v.y, sv.y), -lim, lim);
-  return r;
-}
-
-// first input sample j whose up tap t = U * j + DELTA - i lies in [0, TU) (flrelu.hip up_first)
-template <int U, int DELTA> __host__ __device__ constexpr int r2_up_first(int i) {
-  return i < DELTA ? 0 : (i - DELTA + U - 1) / U;
-}
-
 template <int U, int TU, int TOY, int TOX> struct R2Geom {
   static constexpr int RAY = (TOY - 1) * R2_D + R2_TD;  // activated-grid rows / columns of one tile
   static constexpr int RAX = (TOX - 1) * R2_D + R2_TD;
@@ -110,7 +55,7 @@ __global__ void __launch_bounds__(R2_THREADS) flrelu_radial_kernel(Flr2dArgs a) 
   static_assert(TU % U == 0 && TOY % RY == 0, "whole polyphase phases, whole row groups");
   using G = R2Geom<U, TU, TOY, TOX>;
   using LT = typename std::conditional<std::is_same<TI, float>::value, f2v, h2v>::type;
-  using LP = Lds2<LT>;
+  using LP = LdsPair<LT>;
   constexpr int RAY = G::RAY, RAX = G::RAX, NINY = G::NINY, NINX = G::NINX, PH = G::PH, ROW = G::ROW;
   constexpr int NCG = R2_NCG, D = R2_D, TD = R2_TD;
   __shared__ __attribute__((aligned(16))) LT buf[RAY * ROW];
@@ -122,13 +67,8 @@ __global__ void __launch_bounds__(R2_THREADS) flrelu_radial_kernel(Flr2dArgs a) 
     for (int t = 0; t < TD * TD; ++t) taps[t] = a.gd[t];
   }
 
-  int bid = blockIdx.x;
-  const int cb = bid % a.cblocks;
-  bid /= a.cblocks;
-  const int tx = bid % a.tiles_x;
-  bid /= a.tiles_x;
-  const int ty = bid % a.tiles_y;
-  const int n = bid / a.tiles_y;
+  const FlrBlock blk = flr_block(a);
+  const int cb = blk.cb, tx = blk.tx, ty = blk.ty, n = blk.n;
 
   const int oy0 = ty * TOY, ox0 = tx * TOX;
   const int sy0 = (oy0 * D - a.py0 + DELTA) / U;  // exact: DELTA == p0 (mod U) and U divides the tile origin * D
@@ -155,15 +95,7 @@ __global__ void __launch_bounds__(R2_THREADS) flrelu_radial_kernel(Flr2dArgs a) 
       in[j] = ok ? v : f2v{0.f, 0.f};
     }
 #pragma unroll
-    for (int i = 0; i < RAY; ++i) {
-      f2v acc = f2v{0.f, 0.f};
-#pragma unroll
-      for (int m = 0; m < TU / U; ++m) {
-        const int j = r2_up_first<U, DELTA>(i) + m;
-        if (j < NINY) acc += a.gu[U * j + DELTA - i] * in[j];
-      }
-      buf[i * ROW + xs * NCG + cg] = LP::pack(acc);
-    }
+    for (int i = 0; i < RAY; ++i) buf[i * ROW + xs * NCG + cg] = LP::pack(up_fir<U, TU, DELTA, NINY>(a.gu, i, in));
   }
   __syncthreads();
 
@@ -175,15 +107,9 @@ __global__ void __launch_bounds__(R2_THREADS) flrelu_radial_kernel(Flr2dArgs a) 
 #pragma unroll
     for (int j = 0; j < NINX; ++j) in[j] = LP::unpack(buf[i * ROW + j * NCG + cg]);
 #pragma unroll
-    for (int k = 0; k < RAX; ++k) {
-      f2v v = f2v{0.f, 0.f};
-#pragma unroll
-      for (int m = 0; m < TU / U; ++m) {
-        const int j = r2_up_first<U, DELTA>(k) + m;
-        if (j < NINX) v += a.gu[U * j + DELTA - k] * in[j];
-      }
-      buf[i * ROW + ((k & 1) * PH + (k >> 1)) * NCG + cg] = LP::pack(act_pair(v, a.slope, a.lim));
-    }
+    for (int k = 0; k < RAX; ++k)
+      buf[i * ROW + ((k & 1) * PH + (k >> 1)) * NCG + cg] =
+          LP::pack(act2(up_fir<U, TU, DELTA, NINX>(a.gu, k, in), a.slope, a.lim));
   }
   __syncthreads();
 
@@ -224,7 +150,7 @@ __global__ void __launch_bounds__(R2_THREADS) flrelu_radial_kernel(Flr2dArgs a) 
 #pragma unroll
     for (int r = 0; r < RY; ++r) {
       const int gy = oy0 + rg * RY + r;
-      if (gy < a.out_h) store_pair<TO>(pout + (int64_t)gy * a.ysy, o[r] * ps);
+      if (gy < a.out_h) store_pair_fwd<TO>(pout + (int64_t)gy * a.ysy, o[r] * ps);
     }
   }
 }
@@ -288,8 +214,8 @@ int flrelu_2d_common(const void* x, void* y, int dtype_in, int dtype_out, bool i
                 "%s: unsupported taps %d / %d x %d (at most 24 / 12 x 12)", name, fu_taps, fd_taps, fd_taps);
   IC2_CHECK_ARG(rank >= 0 && rank <= R2_MAX_RANK, "%s: rank %d (0 = direct, at most %d)", name, rank, R2_MAX_RANK);
   IC2_CHECK_ARG(rank == 0 || (fd_v && fd_h), "%s: rank %d without its tap vectors", name, rank);
-  const int64_t ew = ((int64_t)in_w * up + px0 + px1 - (fu_taps - 1) - (fd_taps - 1) + (down - 1)) / down;
-  const int64_t eh = ((int64_t)in_h * up + py0 + py1 - (fu_taps - 1) - (fd_taps - 1) + (down - 1)) / down;
+  const int64_t ew = flr_out_size(in_w, up, px0, px1, fu_taps, fd_taps, down);
+  const int64_t eh = flr_out_size(in_h, up, py0, py1, fu_taps, fd_taps, down);
   IC2_CHECK_ARG(out_h == eh && out_w == ew, "%s: output %dx%d, expected %lldx%lld", name, out_h, out_w, (long long)eh,
                 (long long)ew);
   IC2_CHECK_ARG(out_h > 0 && out_w > 0, "%s: empty output", name);
@@ -303,7 +229,7 @@ int flrelu_2d_common(const void* x, void* y, int dtype_in, int dtype_out, bool i
     set_error("%s: px0 and py0 differ mod up", name);
     return IC2_E_UNSUPPORTED;
   }
-  if (!(slope >= 0.f && slope <= 1.f && gain > 0.f)) {
+  if (!flr_act_ok(slope, gain)) {
     set_error("%s: fused path needs 0 <= slope <= 1 and gain > 0", name);
     return IC2_E_UNSUPPORTED;
   }
@@ -333,11 +259,9 @@ int flrelu_2d_common(const void* x, void* y, int dtype_in, int dtype_out, bool i
   a.tiles_x = a.tiles_y = a.cblocks = 0;
   a.slope = slope;
   // the gain rides on the down taps, the clamp bound is divided by it; the f16 LDS tile holds at most the f16 range
-  a.lim = clamp >= 0.f ? clamp / gain : INFINITY;
+  a.lim = flr_lim(clamp, gain);
   if (p16 && !(a.lim < 65504.f)) a.lim = 65504.f;
-  // NOTE: fu / fd are HOST pointers (layer constants; they travel in the kernarg)
-  for (int t = 0; t < 24; ++t) a.gu[t] = 0.f;
-  for (int t = 0; t < fu_taps; ++t) a.gu[t] = (flip ? fu[t] : fu[fu_taps - 1 - t]) * (float)up;
+  flr_up_taps(a.gu, fu, fu_taps, up, flip);
   for (int ty = 0; ty < R2_TD; ++ty)
     for (int tx = 0; tx < R2_TD; ++tx)
       a.gd[tx * R2_TD + ty] = (flip ? fd[ty * R2_TD + tx] : fd[(R2_TD - 1 - ty) * R2_TD + (R2_TD - 1 - tx)]) * gain;

@@ -19,7 +19,7 @@ The bound, per output element:
 
 eps_op   unit roundoff of the path's operands and intermediates: 2^-11 (f16) for both MFMA kernels (f16 taps, f16
          V / U / D images); 2^-24 for the f32 VALU instances; 2^-8 (bf16) for the bf16 VALU instances, whose LDS
-         image holds packed bf16 pairs (flrelu.hip LdsPair<uint32_t>: the vertically up-sampled input and the
+         image holds packed bf16 pairs (flrelu_valu.h LdsPair<uint32_t>: the vertically up-sampled input and the
          horizontally down-sampled activation are both rounded to bf16).
 eps_out  unit roundoff of the stored output (2^-8 bf16, 2^-11 f16, 2^-24 f32).
 F        absolute floor of the MFMA paths for f16 intermediates below 2^-14 (subnormal: absolute error up to the
