@@ -8,7 +8,9 @@ Drop-in classes (same names / signatures as the reference modules):
   sg3_ops:                    bias_act, upfirdn2d, filtered_lrelu  (torch_utils.ops mirrors)
   cabac_compression:          ContextModel, cabac_encode / cabac_decode, CABACCompressor (native range coder)
   legacy:                     load_network_pkl (SG3 pickle loader that executes nothing from the file)
-  metrics:                    uint8_quality, ssim, evaluate_compression (the PSNR + SSIM record of test_compression)
+  metrics:                    uint8_quality, ssim, evaluate_compression (the PSNR + SSIM record of test_compression);
+                              ms_ssim_terms, uint8_ms_ssim, ms_ssim (the MS-SSIM figure), ms_ssim_loss, MSSSIMLoss
+                              (1 - MS-SSIM with a HIP backward: the perceptual training term that works offline)
 All compute runs in libic2ops.so (hand-written HIP for gfx950); ROCm tensors only.
 """
 from . import _native  # noqa: F401
@@ -21,9 +23,11 @@ from . import sg3_ops  # noqa: F401
 from .cabac_compression import CABACCompressor, ContextModel, cabac_encode, cabac_decode  # noqa: F401
 from . import legacy  # noqa: F401
 from .metrics import uint8_quality, ssim, ssim_from_sums, evaluate_compression  # noqa: F401
+from .metrics import ms_ssim_terms, uint8_ms_ssim, ms_ssim, ms_ssim_loss, MSSSIMLoss, MS_SSIM_TILE  # noqa: F401
 
 __all__ = ["HVAE_VGG_Encoder", "VGGBlock", "HierarchyProjector", "StyleGAN3Compressor", "save_tensor_as_image",
            "GumbelSoftmaxDiscretization", "GumbelSoftmaxCompressor", "Generator", "SynthesisNetwork",
            "SynthesisLayer", "SynthesisInput", "MappingNetwork", "FullyConnectedLayer", "make_generator", "SG3_R_KWARGS",
            "quantize_uniform", "resize_bilinear", "sg3_ops", "CABACCompressor", "ContextModel", "cabac_encode",
-           "cabac_decode", "legacy", "uint8_quality", "ssim", "ssim_from_sums", "evaluate_compression"]
+           "cabac_decode", "legacy", "uint8_quality", "ssim", "ssim_from_sums", "evaluate_compression",
+           "ms_ssim_terms", "uint8_ms_ssim", "ms_ssim", "ms_ssim_loss", "MSSSIMLoss", "MS_SSIM_TILE"]

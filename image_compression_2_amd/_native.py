@@ -101,6 +101,10 @@ _SIGS = {
     "ic2_uint8_sse": [_P, _P, _I64, _I64, _P, _P, _P],
     "ic2_uint8_quality_scratch_doubles": [_I64, _I, _I, _I, _I],
     "ic2_uint8_quality": [_P, _P, _I64, _I, _I, _I, _I, _P, _P, _P, _P],
+    "ic2_ms_ssim_ws_floats": [_I64, _I, _I, _I],
+    "ic2_ms_ssim_fwd": [_P, _P, _I, _I64, _I, _I, _I, _P, _P, _P],
+    "ic2_ms_ssim_bwd_ws_floats": [_I64, _I, _I, _I],
+    "ic2_ms_ssim_bwd": [_P, _P, _I, _P, _P, _I64, _I, _I, _I, _P, _P, _P, _P],
     "ic2_resize_bilinear": [_P, _P, _I64, _I, _I, _I, _I, _P],
     "ic2_rc_bound": [_I64, _I64],
     "ic2_rc_encode": [_P, _I64, _I, _I, _I, _P, _I64, _P, _I],
@@ -135,6 +139,7 @@ _SIGS = {
 }
 _RESTYPE = {"ic2_conv_plan": ctypes.c_char_p, "ic2_conv_wino_plan": ctypes.c_char_p, "ic2_conv_igemm_ws_bytes": _I64, "ic2_group_norm_stats_floats": _I64, "ic2_global_avg_pool_floats": _I64,
             "ic2_uint8_sse_scratch_doubles": _I64, "ic2_uint8_quality_scratch_doubles": _I64,
+            "ic2_ms_ssim_ws_floats": _I64, "ic2_ms_ssim_bwd_ws_floats": _I64,
             "ic2_rc_bound": _I64, "ic2_conv_wgrad_ws_floats": _I64,
             "ic2_gn_lrelu_pool_bwd_floats": _I64, "ic2_conv3x3_gn_stats_floats": _I64,
             "ic2_flrelu_bwd_ydot_floats": _I64, "ic2_flrelu_bwd_2d_ydot_floats": _I64,

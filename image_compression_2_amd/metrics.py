@@ -5,7 +5,12 @@ K1 = 0.01, K2 = 0.03, the mean of the SSIM map over the windows that lie fully i
 The per-image squared-error sums run in one HIP kernel (ic2_uint8_sse); ic2_uint8_quality gives them together with
 the per-(image, channel) SSIM-map sums in one pass over both images.  The log, the division by the window count and
 the channel mean are host arithmetic.  ``evaluate_compression`` restates the record of the reference's
-``test_compression`` (hvae_training.py:342-424) for a batch."""
+``test_compression`` (hvae_training.py:342-424) for a batch.
+
+MS-SSIM, the third figure the reference's README reports, runs on the same footing (ic2_ms_ssim_fwd / ic2_ms_ssim_bwd,
+csrc/msssim.hip): ``ms_ssim_terms`` gives the per-(image, channel, scale) terms, ``uint8_ms_ssim`` / ``ms_ssim`` the
+evaluation figure on the uint8 images, and ``ms_ssim_loss`` / ``MSSSIMLoss`` the differentiable 1 - MS-SSIM with a HIP
+backward: the perceptual training term that needs no pretrained weights (``training.train_step(percep=...)``)."""
 from __future__ import annotations
 
 import math
@@ -16,6 +21,13 @@ from . import _native as nv
 
 # window origins (rows, columns) one workgroup of ic2_uint8_quality owns: QT_OY x QT_OX of csrc/metrics.hip
 QUALITY_TILE = (32, 64)
+# map positions (rows, columns) one workgroup of ic2_ms_ssim_fwd owns per scale: MT_Y x MT_X of csrc/msssim.hip
+MS_SSIM_TILE = (32, 32)
+# the exponents of the five scales (Wang, Simoncelli, Bovik 2003), finest first
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+# the smaller image side must exceed (11 - 1) * 2^4: the fifth scale holds at least one 11 x 11 window
+MS_SSIM_MIN_SIDE = 161
+_MS_LOSS, _MS_METRIC = 0, 1    # ic2ops.h IC2_MS_SSIM_LOSS / IC2_MS_SSIM_METRIC
 
 
 def uint8_sse(a, b):
@@ -86,6 +98,160 @@ def ssim(a, b, win_size=7):
     return sum(per_image) / len(per_image)
 
 
+def _ms_refuse_capture(t):
+    """The Python layer of MS-SSIM is not capturable: it forms the value and d L / d terms with float64 torch ops and,
+    for the loss, runs its backward from the autograd engine's thread, and a capture of exactly that ended in a host
+    segmentation fault inside the capture's end on the MI355X whose cause is not established.  Refuse before anything
+    is launched instead.  ic2_ms_ssim_fwd / ic2_ms_ssim_bwd on caller-owned buffers are capturable (they neither
+    allocate nor synchronise; tests/test_gpu_ms_ssim.py replays them from a graph bit for bit)."""
+    if t.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("ms_ssim: the Python layer (ms_ssim_terms, uint8_ms_ssim, ms_ssim, ms_ssim_loss, MSSSIMLoss) "
+                           "refuses to run inside a graph capture; run it outside the capture, or capture "
+                           "ic2_ms_ssim_fwd / ic2_ms_ssim_bwd on preallocated buffers (metrics._ms_refuse_capture)")
+
+
+def _ms_ssim_check(a, b):
+    nv.require_gpu(a, b)
+    _ms_refuse_capture(a)
+    if a.shape != b.shape or a.dim() != 4:
+        raise ValueError(f"ms_ssim: expected two NCHW batches of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n, c, h, w = a.shape
+    if min(n, c) < 1 or min(h, w) < MS_SSIM_MIN_SIDE:
+        raise ValueError(f"ms_ssim: shape {tuple(a.shape)}: the batch must not be empty and the smaller image side "
+                         f"must exceed (11 - 1) * 2^4 = {MS_SSIM_MIN_SIDE - 1} for five scales")
+    return n, c, h, w
+
+
+def _ms_ssim_forward(a, b, mode):
+    """a, b: contiguous f32 NCHW on the device -> (terms f64 [N, C, 5], the forward workspace)."""
+    n, c, h, w = _ms_ssim_check(a, b)
+    terms = torch.empty([n, c, 5], dtype=torch.float64, device=a.device)
+    # float64 storage: the workspace starts with the f64 partials (8-byte aligned)
+    ws = torch.empty((int(nv.query("ic2_ms_ssim_ws_floats", n, c, h, w)) + 1) // 2, dtype=torch.float64,
+                     device=a.device)
+    nv.call("ic2_ms_ssim_fwd", nv.ptr(a), nv.ptr(b), mode, n, c, h, w, nv.ptr(terms), nv.ptr(ws), nv.stream_of(a))
+    return terms, ws
+
+
+_ms_weight_cache = {}
+
+
+def _ms_weights(device):
+    """MS_SSIM_WEIGHTS as a float64 device tensor, uploaded once per device (no host-to-device copy per call)."""
+    key = (device.type, device.index)
+    if key not in _ms_weight_cache:
+        _ms_weight_cache[key] = torch.tensor(MS_SSIM_WEIGHTS, dtype=torch.float64, device=device)
+    return _ms_weight_cache[key]
+
+
+def _ms_ssim_value(terms):
+    """terms f64 [N, C, 5] -> per-image value f64 [N]: mean over channels of prod_s max(t_s, 0) ** w_s."""
+    wts = _ms_weights(terms.device)
+    return (terms.clamp_min(0) ** wts).prod(dim=2).mean(dim=1)
+
+
+def ms_ssim_terms(a, b, uint8=True):
+    """The five MS-SSIM terms per (image, channel) of two NCHW batches in nominal [-1, 1] -> float64 [N, C, 5] on the
+    device: the spatial mean of cs at scales 0..3 and of ssim at scale 4 (11-tap Gaussian window, sigma 1.5, no
+    padding; 2 x 2 mean pool between scales, an odd axis padded by one zero at both ends).  ``uint8=True`` scores the
+    reference's uint8 images with data range 255 (the metric); ``uint8=False`` scores x*0.5+0.5 unclamped with data
+    range 1 (what ``ms_ssim_loss`` differentiates).  Shapes whose smaller side is below 161 raise ValueError.  Not
+    capturable in a graph: inside a capture this raises RuntimeError (``_ms_refuse_capture``)."""
+    _ms_refuse_capture(a)
+    a = a.to(torch.float32).contiguous()
+    b = b.to(torch.float32).contiguous()
+    return _ms_ssim_forward(a, b, _MS_METRIC if uint8 else _MS_LOSS)[0]
+
+
+def uint8_ms_ssim(a, b):
+    """Per-image MS-SSIM of the uint8 images -> float64 [N] on the device: mean over channels of
+    prod_s max(t_s, 0) ** w_s with the weights ``MS_SSIM_WEIGHTS``."""
+    return _ms_ssim_value(ms_ssim_terms(a, b, uint8=True))
+
+
+def ms_ssim(a, b):
+    """Mean over the batch of the per-image MS-SSIMs (the counterpart of ``ssim``)."""
+    per_image = uint8_ms_ssim(a, b).tolist()
+    return sum(per_image) / len(per_image)
+
+
+class _MSSSIMLossBackwardFn(torch.autograd.Function):
+    """ic2_ms_ssim_bwd as a graph node of its own: a second differentiation (create_graph=True) reaches a backward
+    that refuses instead of silently treating the gradient as a constant."""
+
+    @staticmethod
+    def forward(ctx, grad_out, a, b, ws, terms, need_a, need_b):
+        _ms_refuse_capture(a)
+        n, c, h, w = a.shape
+        wts = _ms_weights(terms.device)
+        # d value_c / d t_s = w_s * value_c / t_s where all five terms are positive, 0 where any is not (the product
+        # is 0 there and max(t, 0) ** w has no finite derivative at 0)
+        alive = (terms > 0).all(dim=2, keepdim=True)
+        safe = torch.where(alive, terms, torch.ones_like(terms))
+        value_c = (safe ** wts).prod(dim=2, keepdim=True)
+        upstream = (-grad_out.to(torch.float64) / c).view(n, 1, 1)
+        gterms = torch.where(alive, upstream * wts * value_c / safe, torch.zeros_like(terms)).contiguous()
+        ga = torch.empty_like(a) if need_a else None
+        gb = torch.empty_like(b) if need_b else None
+        ws_grad = torch.empty(max(int(nv.query("ic2_ms_ssim_bwd_ws_floats", n, c, h, w)), 1), dtype=torch.float32,
+                              device=a.device)
+        nv.call("ic2_ms_ssim_bwd", nv.ptr(a), nv.ptr(b), _MS_LOSS, nv.ptr(ws), nv.ptr(gterms), n, c, h, w, nv.ptr(ga),
+                nv.ptr(gb), nv.ptr(ws_grad), nv.stream_of(a))
+        return ga, gb
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise nv.AutogradUnsupported("ms_ssim_loss: double backward (differentiating its gradient) is not implemented "
+                                     "on the HIP path")
+
+
+class _MSSSIMLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        terms, ws = _ms_ssim_forward(a, b, _MS_LOSS)
+        ctx.save_for_backward(a, b, ws, terms)
+        return (1.0 - _ms_ssim_value(terms)).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a, b, ws, terms = ctx.saved_tensors
+        return _MSSSIMLossBackwardFn.apply(grad_out, a, b, ws, terms, ctx.needs_input_grad[0],
+                                           ctx.needs_input_grad[1])
+
+
+def ms_ssim_loss(a, b):
+    """1 - MS-SSIM per image -> float32 [N], differentiable with respect to either or both inputs (HIP forward and
+    backward).  a, b: NCHW in nominal [-1, 1]; the images scored are x*0.5+0.5, unclamped, with data range 1 (the
+    metric's uint8 truncation has no gradient).  Only the gradients autograd asks for are computed.
+
+    Gradient convention (a deviation from the plain chain rule): prod_s max(t_s, 0) ** w_s has no finite derivative
+    at t_s = 0, so where any of a channel's five terms is <= 0 that channel's product is 0 and its gradient is defined
+    as 0; everywhere else the gradient is the chain rule's.  Differentiating the backward again raises.
+
+    Inputs of another dtype (the f16 reconstruction of the loss-scaled training step) are cast to float32 by torch, one
+    elementwise pass over the image each way; the kernels read float32.
+
+    Not capturable: called while the current stream is capturing a graph (a captured training step, for instance),
+    forward or backward, this raises RuntimeError before anything is launched (``_ms_refuse_capture`` says why).  The
+    two C entry points on caller-owned buffers are the capturable interface."""
+    _ms_refuse_capture(a)
+    a = a.to(torch.float32).contiguous()
+    b = b.to(torch.float32).contiguous()
+    _ms_ssim_check(a, b)
+    if not (torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)):
+        return (1.0 - _ms_ssim_value(_ms_ssim_forward(a, b, _MS_LOSS)[0])).to(torch.float32)
+    return _MSSSIMLossFn.apply(a, b)
+
+
+class MSSSIMLoss(torch.nn.Module):
+    """``ms_ssim_loss`` as the ``percep`` callable of ``training.train_step`` / ``train_step_gumbel``:
+    ``MSSSIMLoss()(images, reconstructed)`` -> float32 [N].  No parameters, no pretrained weights.  Like
+    ``ms_ssim_loss`` it refuses to run inside a graph capture (RuntimeError): a step that uses it is run eagerly."""
+
+    def forward(self, images, reconstructed):
+        return ms_ssim_loss(images, reconstructed)
+
+
 # layout of the all-reduced quality record (distributed.metric_vector with `extra`): the quantized reconstruction's
 # squared error leads, as in the benchmark's metric vector
 _Q_SSE_Q, _Q_NVAL, _Q_NIMG, _Q_SSIM_Q, _Q_NWIN, _Q_SSE_NQ, _Q_SSIM_NQ = range(7)
@@ -111,7 +277,8 @@ def figures_from_record(vec):
             "batch_ssim_quantized": ssim_from_sums(v[_Q_SSIM_Q], v[_Q_NWIN])}
 
 
-def evaluate_compression(compressor, x, quantization_bits=8, noise_mode="const", reduce=False, win_size=7):
+def evaluate_compression(compressor, x, quantization_bits=8, noise_mode="const", reduce=False, win_size=7,
+                         ms_ssim=False):
     """The record of the reference's ``test_compression`` (hvae_training.py:342-424) for a batch ``x`` [N, C, H, W]:
     reconstruct without quantization, compress, decompress, and score both reconstructions against ``x``.
 
@@ -120,7 +287,12 @@ def evaluate_compression(compressor, x, quantization_bits=8, noise_mode="const",
     ``psnr_*`` / ``ssim_*`` are per-image lists (the reference scores one image at a time).  The ``batch_*`` figures
     come from the sums over the batch: the PSNR of the pooled MSE (as ``psnr``) and the mean SSIM.  With
     ``reduce=True`` those sums are all-reduced over the process group first, so every rank reports the figures of the
-    global batch (``n_images`` counts it); the per-image lists stay local."""
+    global batch (``n_images`` counts it); the per-image lists stay local.
+
+    ``ms_ssim=True`` adds the third figure the reference's README reports: ``ms_ssim_no_quant`` / ``ms_ssim_quantized``
+    (per-image lists, ``uint8_ms_ssim``) and ``batch_ms_ssim_*`` (the mean over the images; with ``reduce=True`` from
+    the all-reduced sum and image count).  It needs images whose smaller side exceeds 160.  With the default the
+    record is key for key what it was."""
     from . import distributed as icd
     from .stylegan3_hvae_full import resize_bilinear
     with torch.no_grad():
@@ -128,12 +300,14 @@ def evaluate_compression(compressor, x, quantization_bits=8, noise_mode="const",
         w_quantized = compressor.compress(x, quantization_bits)
         recon_quantized = compressor.decompress(w_quantized, noise_mode=noise_mode)
         n, c, h, w = x.shape
-        sums = []
+        sums, ms_values = [], []
         for img in (recon, recon_quantized):
             if img.shape[2:] != x.shape[2:]:
                 img = resize_bilinear(img, (h, w))
             sse, ssim_sum = _uint8_quality_sums(img, x, win_size)
             sums.append((sse.cpu(), ssim_sum.cpu()))
+            if ms_ssim:
+                ms_values.append(uint8_ms_ssim(img, x).cpu())
     n_win = n_windows(h, w, int(win_size))
     per_image_values = c * h * w
     res = compressor.generator.img_resolution
@@ -152,4 +326,11 @@ def evaluate_compression(compressor, x, quantization_bits=8, noise_mode="const",
     if reduce:
         vec = icd.allreduce_sum(vec, device=x.device)
     out.update(figures_from_record(vec))
+    if ms_ssim:
+        ms_vec = torch.tensor([v.sum().item() for v in ms_values] + [float(n)], dtype=torch.float64)
+        if reduce:
+            ms_vec = icd.allreduce_sum(ms_vec, device=x.device)
+        for i, name in enumerate(("no_quant", "quantized")):
+            out["ms_ssim_" + name] = ms_values[i].tolist()
+            out["batch_ms_ssim_" + name] = float(ms_vec[i]) / float(ms_vec[2])
     return out

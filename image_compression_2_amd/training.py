@@ -13,7 +13,9 @@ Per batch, as the reference:
 
 Deviations, all explicit:
   * LPIPS(net='vgg') needs pretrained VGG weights that cannot be fetched here (no network): ``percep`` is a
-    caller-supplied callable; with ``percep=None`` a non-zero ``perceptual_weight`` raises.
+    caller-supplied callable; with ``percep=None`` a non-zero ``perceptual_weight`` raises.  The perceptual term
+    that works offline is ``metrics.MSSSIMLoss()``: 1 - MS-SSIM per image with a HIP forward and backward, no
+    pretrained weights (``train_step(..., percep=metrics.MSSSIMLoss())``; images of at least 161 x 161).
   * Without fp16 the reference runs its forward under ``torch.no_grad()`` (:668) and its loss.backward()
     then fails; this step always builds the graph.  Precision: ``precision='bf16'`` on the modules (no loss
     scaling needed), or the reference's fp16 branch (:487, :669, :693-696: autocast + GradScaler) as f16

@@ -409,6 +409,30 @@ int64_t ic2_uint8_quality_scratch_doubles(int64_t n_img, int c, int h, int w, in
 int ic2_uint8_quality(const float* a, const float* b, int64_t n_img, int c, int h, int w, int win, double* sse_out,
                       double* ssim_sum_out, double* scratch, void* stream);
 
+/* MS-SSIM (the reference's README reports PSNR, MS-SSIM and LPIPS): five scales, 11-tap Gaussian window (sigma 1.5,
+ * normalised, separable, no padding), K1 = 0.01, K2 = 0.03, a 2 x 2 mean pool between scales that pads an odd axis by
+ * one zero at both ends (output i covers inputs 2i-1, 2i; length (s+1)/2).  a, b: NCHW f32 [n][c][h][w], nominal
+ * [-1, 1].  mode IC2_MS_SSIM_LOSS: the images are x*0.5+0.5 (unclamped), data range 1.  mode IC2_MS_SSIM_METRIC: the
+ * uint8 conversion of ic2_uint8_quality, data range 255.
+ * ic2_ms_ssim_fwd (metrics.ms_ssim_terms, metrics.uint8_ms_ssim, metrics.ms_ssim, metrics.ms_ssim_loss): terms
+ * [n][c][5] (f64) = the spatial mean of cs at scales 0..3 and of ssim at scale 4.  The weights, the relu, the product
+ * and the channel mean are the caller's.  ws: ic2_ms_ssim_ws_floats() floats, 8-byte aligned; it receives the f64
+ * per-tile partials (summed in a fixed order, no atomics) and the pooled levels 1..4 of both images, which
+ * ic2_ms_ssim_bwd reads.  Identical images give every term exactly 1.0.
+ * ic2_ms_ssim_bwd (metrics.ms_ssim_loss's backward): gterms [n][c][5] (f64) = d L / d terms -> ga, gb [n][c][h][w]
+ * (f32) = d L / d a, d L / d b; either may be NULL and is then not computed.  a, b, n, c, h, w and ws_fwd as the forward
+ * call had them; ws_grad: ic2_ms_ssim_bwd_ws_floats() floats (the gradient planes of levels 1..4).  Loss mode only:
+ * IC2_MS_SSIM_METRIC returns IC2_E_UNSUPPORTED (the truncation has zero gradient).
+ * IC2_E_INVALID, before any launch: null pointer, non-positive size, min(h, w) <= (11-1) * 2^4 = 160, unknown mode.
+ * The queries return 0 for such a shape. */
+enum { IC2_MS_SSIM_LOSS = 0, IC2_MS_SSIM_METRIC = 1 };
+int64_t ic2_ms_ssim_ws_floats(int64_t n, int c, int h, int w);
+int ic2_ms_ssim_fwd(const float* a, const float* b, int mode, int64_t n, int c, int h, int w, double* terms, float* ws,
+                    void* stream);
+int64_t ic2_ms_ssim_bwd_ws_floats(int64_t n, int c, int h, int w);
+int ic2_ms_ssim_bwd(const float* a, const float* b, int mode, const float* ws_fwd, const double* gterms, int64_t n,
+                    int c, int h, int w, float* ga, float* gb, float* ws_grad, void* stream);
+
 /* F.interpolate(mode='bilinear', align_corners=False, no antialias) of StyleGAN3Compressor.forward
  * (stylegan3_hvae_full.py:277-279), NCHW f32. */
 int ic2_resize_bilinear(const float* x, float* y, int64_t nc, int h, int w, int oh, int ow, void* stream);
