@@ -181,13 +181,30 @@ def exported_symbols():
     return ["ic2_last_error"] + list(_SIGS)
 
 
+E_UNSUPPORTED = 2   # ic2ops.h IC2_E_UNSUPPORTED: no instance for these arguments, nothing written
+
+
 def call(name, *args):
     lib = load()
     rc = getattr(lib, name)(*args)
     if rc != 0:
         msg = lib.ic2_last_error().decode(errors="replace")
-        raise RuntimeError(f"{name} failed (code {rc}): {msg}")
+        err = RuntimeError(f"{name} failed (code {rc}): {msg}")
+        err.code = rc
+        raise err
     return rc
+
+
+def try_call(name, *args):
+    """call() for entry points that may have no instance for a geometry: False on IC2_E_UNSUPPORTED (the caller
+    composes the op from others), True when it ran; any other status raises."""
+    try:
+        call(name, *args)   # the module attribute, looked up now: an instrumented pass may have replaced it
+    except RuntimeError as e:
+        if getattr(e, "code", None) != E_UNSUPPORTED:
+            raise
+        return False
+    return True
 
 
 def query(name, *args):
@@ -332,19 +349,28 @@ def ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+# torch's raw current-stream accessor (private; present in torch 2.10.0+rocm7.0, the version this was checked against):
+# without it stream_of falls back to the public torch.cuda.current_stream
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
 def stream_of(t=None):
-    dev = t.device if t is not None else None
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    """The hipStream_t (as an int: ctypes passes it as void*) torch would launch on for t's device.  Asked once per
+    native launch, so through the raw accessor where t names a device (no torch.cuda.Stream object is built)."""
+    idx = t.device.index if t is not None else None
+    if idx is not None and _raw_stream is not None:
+        return _raw_stream(idx)
+    return torch.cuda.current_stream(t.device if t is not None else None).cuda_stream
+
+
+_DTYPE_CODES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
 
 def dtype_code(dt):
-    if dt == torch.float32:
-        return F32
-    if dt == torch.bfloat16:
-        return BF16
-    if dt == torch.float16:
-        return F16
-    raise TypeError(f"unsupported dtype {dt}")
+    try:
+        return _DTYPE_CODES[dt]
+    except KeyError:
+        raise TypeError(f"unsupported dtype {dt}") from None
 
 
 def torch_dtype(precision):

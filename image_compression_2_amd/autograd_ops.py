@@ -27,11 +27,11 @@ their styles only:
 from __future__ import annotations
 
 import contextlib
-import ctypes
 
 import torch
 
 from . import _native as nv
+from . import ops
 
 
 def _pad_to(c_p, t):
@@ -41,22 +41,12 @@ def _pad_to(c_p, t):
 def pack_conv_weight_adjoint(weight, cout_p, cin_p, dt):
     """[cout][cin][kh][kw] f32 -> the dgrad pack [cin_p][kh][kw][cout_p] (dt): W flipped in space and transposed in
     channels, gathered in one launch (ic2_pack_weight_adjoint)."""
-    w = weight.detach().to(torch.float32).contiguous()
-    cout, cin, kh, kw = w.shape
-    out = torch.empty([cin_p, kh, kw, cout_p], dtype=dt, device=w.device)
-    nv.call("ic2_pack_weight_adjoint", nv.ptr(w), cout, cin, kh, kw, cin_p, cout_p, nv.ptr(out), nv.dtype_code(dt),
-            nv.stream_of(w))
-    return out
+    return ops.pack_weight_adjoint(weight, cin_p, cout_p, dt)
 
 
 def pack_conv_weight(weight, cin_p, cout_p, dt):
     """[cout][cin][kh][kw] f32 -> packed [cout_p][kh][kw][cin_p] (dt) on the device."""
-    w = weight.detach().to(torch.float32).contiguous()
-    cout, cin, kh, kw = w.shape
-    out = torch.empty([cout_p, kh, kw, cin_p], dtype=dt, device=w.device)
-    nv.call("ic2_pack_weight", nv.ptr(w), cout, cin, kh, kw, cout_p, cin_p, 0, 1.0, nv.ptr(out), nv.dtype_code(dt),
-            None, nv.stream_of(w))
-    return out
+    return ops.pack_weight(weight, cout_p, cin_p, dt)
 
 
 _DERIVED = None  # dict while a derived_cache() block is active
@@ -117,16 +107,8 @@ def conv_nhwc(x, wp, bias_p, cout_valid, kh, pad, dt_out=None, wino=None, grad=F
     ho, wo = h + 2 * pad - kh + 1, w + 2 * pad - kh + 1
     dt_out = x.dtype if dt_out is None else dt_out
     y = torch.empty([n, ho, wo, cout_p], dtype=dt_out, device=x.device)
-    odt = nv.F16_IEEE if grad and dt_out == torch.float16 else nv.dtype_code(dt_out)
-    if wino is not None and nv.wino_preferred(nv.dtype_code(x.dtype), n, h, w, cin_p, cout_p, kh, kh, pad):
-        nv.conv_wino(nv.ptr(x), nv.ptr(wino()), nv.ptr(y), nv.dtype_code(x.dtype), odt, n, h, w,
-                     cin_p, cout_p, cout_valid, pad, ho, wo, None, nv.ptr(bias_p), 0, 0.0, 1.0, -1.0, 1.0, nv.NHWC,
-                     nv.stream_of(x))
-        return y
-    nv.conv_igemm(nv.ptr(x), nv.ptr(wp), nv.ptr(y), nv.dtype_code(x.dtype), odt, n, h, w, cin_p,
-                  cout_p, cout_valid, kh, kh, pad, ho, wo, None, nv.ptr(bias_p), 0, 0.0, 1.0, -1.0, 1.0, nv.NHWC,
-                  nv.stream_of(x), x.device)
-    return y
+    return ops.conv(x, wp, y, nv.dtype_code(x.dtype), n, h, w, cin_p, cout_p, cout_valid, kh, pad, bias=bias_p,
+                    wino=wino, out_code=nv.F16_IEEE if grad and dt_out == torch.float16 else None)
 
 
 class Conv2dNHWC(torch.autograd.Function):
@@ -167,11 +149,7 @@ class Conv2dNHWC(torch.autograd.Function):
                            lambda: pack_conv_weight_adjoint(weight, cout_p, cin_p, x.dtype))
             dx = conv_nhwc(dy, wtp, None, cin_p, kh, kh - 1 - ctx.pad, grad=True)
         if ctx.needs_input_grad[1]:
-            nfl = int(nv.query("ic2_conv_wgrad_ws_floats", n, h, w, cin_p, cout_p, kh, kw, ctx.pad))
-            ws = torch.empty([max(nfl, 4)], dtype=torch.float32, device=x.device)
-            dw = torch.empty([cout, cin, kh, kw], dtype=torch.float32, device=x.device)   # the parameter's layout
-            nv.call("ic2_conv_wgrad_oihw", nv.ptr(x), nv.ptr(dy), nv.ptr(dw), nv.dtype_code(x.dtype), n, h, w, cin_p,
-                    cout_p, cout, cin, kh, kw, ctx.pad, nv.ptr(ws), nfl, nv.stream_of(x))
+            dw = ops.wgrad_oihw(x, dy, n, h, w, cin_p, cout_p, cout, cin, (kh, kw), ctx.pad)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             if colsum is not None:   # the GroupNorm backward's f64 channel sums: no pass over dy
                 db = colsum[0][:cout]
@@ -186,16 +164,11 @@ class GroupNormLReluPoolNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, groups, eps, slope, pool, c, dt_out):
         n, h, w, c_p = y.shape
-        stream = nv.stream_of(y)
-        nfl = int(nv.query("ic2_group_norm_stats_floats", n, h * w, groups))
-        stats = torch.empty([nfl], dtype=torch.float32, device=y.device)
-        nv.call("ic2_group_norm_stats", nv.ptr(y), nv.dtype_code(y.dtype), n, h * w, c_p, c, groups, float(eps),
-                nv.ptr(stats), stream)
+        stats = ops.gn_stats(y, n, h * w, c_p, c, groups, eps)
         oh, ow = (h // 2, w // 2) if pool else (h, w)
         out = torch.empty([n, oh, ow, c_p], dtype=dt_out, device=y.device)
         g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        nv.call("ic2_gn_lrelu_pool", nv.ptr(y), nv.ptr(out), nv.dtype_code(y.dtype), nv.dtype_code(dt_out), n, h, w,
-                c_p, c, groups, nv.ptr(stats), nv.ptr(g32), nv.ptr(b32), float(slope), int(pool), stream)
+        ops.gn_lrelu_pool(y, out, nv.dtype_code(dt_out), n, h, w, c_p, c, groups, stats, g32, b32, slope, pool)
         ctx.save_for_backward(y, stats, g32, b32)
         ctx.meta = (groups, slope, pool, c)
         return out
@@ -205,17 +178,8 @@ class GroupNormLReluPoolNHWC(torch.autograd.Function):
         y, stats, g32, b32 = ctx.saved_tensors
         groups, slope, pool, c = ctx.meta
         n, h, w, c_p = y.shape
-        dout = dout.contiguous()
-        nfl = int(nv.query("ic2_gn_lrelu_pool_bwd_floats", n, h, w, c_p, groups))
-        ws = torch.empty([nfl], dtype=torch.float32, device=y.device)
-        dy = torch.empty_like(y)
-        dgamma = torch.empty([c], dtype=torch.float32, device=y.device)
-        dbeta = torch.empty([c], dtype=torch.float32, device=y.device)
-        dsum = torch.empty([c], dtype=torch.float32, device=y.device)
-        nv.call("ic2_gn_lrelu_pool_bwd_db", nv.ptr(y), nv.ptr(dout), nv.ptr(dy), nv.dtype_code(y.dtype),
-                nv.dtype_code(dout.dtype), nv.dtype_code(dy.dtype), n, h, w, c_p, c, groups, nv.ptr(stats),
-                nv.ptr(g32), nv.ptr(b32), float(slope), int(pool), nv.ptr(dgamma), nv.ptr(dbeta), nv.ptr(dsum),
-                nv.ptr(ws), nfl, nv.stream_of(y))
+        dy, dgamma, dbeta, dsum = ops.gn_lrelu_pool_bwd(y, dout.contiguous(), n, h, w, c_p, c, groups, stats, g32, b32,
+                                                        slope, pool)
         # sum of dy over (n, p): the producing conv's bias gradient (Conv2dNHWC.backward reads it instead of
         # reducing dy again); stamped with dy's version so an in-place accumulation into dy invalidates it
         dy._ic2_colsum = (dsum, dy._version)
@@ -228,21 +192,13 @@ class GlobalAvgPoolNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, c):
         n, h, w, c_p = x.shape
-        nfl = int(nv.query("ic2_global_avg_pool_floats", n, h * w, c_p, c))
-        buf = torch.empty([nfl], dtype=torch.float32, device=x.device)
-        nv.call("ic2_global_avg_pool", nv.ptr(x), nv.dtype_code(x.dtype), n, h * w, c_p, c, nv.ptr(buf),
-                nv.stream_of(x))
+        buf = ops.gap(x, nv.dtype_code(x.dtype), n, h * w, c_p, c)
         ctx.shape, ctx.dtype, ctx.c = x.shape, x.dtype, c
         return buf[: n * c].view(n, c).clone()
 
     @staticmethod
     def backward(ctx, dp):
-        n, h, w, c_p = ctx.shape
-        dp = dp.float().contiguous()
-        dx = torch.empty(ctx.shape, dtype=ctx.dtype, device=dp.device)
-        nv.call("ic2_gap_bwd", nv.ptr(dp), nv.ptr(dx), nv.dtype_code(ctx.dtype), n, h * w, c_p, ctx.c,
-                nv.stream_of(dp))
-        return dx, None
+        return ops.gap_bwd(dp.float().contiguous(), ctx.shape, ctx.dtype, ctx.c), None
 
 
 class ToNHWC(torch.autograd.Function):
@@ -250,20 +206,13 @@ class ToNHWC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, dt, c_p):
-        n, c, h, w = x.shape
-        out = torch.empty([n, h, w, c_p], dtype=dt, device=x.device)
-        nv.call("ic2_nchw_to_nhwc", nv.ptr(x), nv.ptr(out), nv.dtype_code(dt), n, c, h, w, c_p, None, nv.stream_of(x))
         ctx.shape = x.shape
-        return out
+        return ops.to_nhwc(x, dt, c_p)
 
     @staticmethod
     def backward(ctx, dy):
         n, c, h, w = ctx.shape
-        dy = dy.contiguous()
-        dx = torch.empty([n, c, h, w], dtype=torch.float32, device=dy.device)
-        nv.call("ic2_nhwc_to_nchw", nv.ptr(dy), nv.dtype_code(dy.dtype), nv.ptr(dx), n, c, h, w, dy.shape[-1],
-                nv.stream_of(dy))
-        return dx, None, None
+        return ops.to_nchw(dy.contiguous(), n, c, h, w, dy.shape[-1]), None, None
 
 
 class GumbelSoftmaxQuantize(torch.autograd.Function):
@@ -284,9 +233,7 @@ class GumbelSoftmaxQuantize(torch.autograd.Function):
         idx = torch.empty(m, dtype=torch.int64, device=zf.device)
         psum = torch.zeros(k, dtype=torch.float32, device=zf.device)
         logt = log_temperature.detach()
-        nv.call("ic2_gumbel_softmax_quantize_dseed", nv.ptr(zf), m, nv.ptr(codebook), k, nv.ptr(logt), 1.0,
-                int(bool(hard)), nv.ptr(seed), 0, nv.ptr(gumbel_noise), nv.ptr(disc), nv.ptr(idx), nv.ptr(psum),
-                nv.stream_of(zf))
+        ops.gumbel_quantize(zf, codebook, logt, hard, seed, gumbel_noise, disc, idx, psum)
         avg_probs = psum / m
         perplexity = torch.exp(-torch.sum(avg_probs * torch.log(avg_probs + 1e-10)))
         ctx.save_for_backward(zf, logt, codebook, seed, psum, perplexity, gumbel_noise)
@@ -308,16 +255,7 @@ class GumbelSoftmaxQuantize(torch.autograd.Function):
             avg = psum / m
             q = ((g_perp.to(torch.float32) * perplexity)
                  * (-(torch.log(avg + 1e-10) + avg / (avg + 1e-10))) / m).contiguous()
-        dz = torch.empty(m, dtype=torch.float32, device=dev)
-        dlogt = ws = None
-        nbytes = 0
-        if ctx.needs_input_grad[1]:
-            nbytes = int(nv.query("ic2_gumbel_softmax_bwd_ws_bytes", m))
-            ws = torch.empty([max(nbytes, 4) // 4], dtype=torch.float32, device=dev)
-            dlogt = torch.empty(1, dtype=torch.float32, device=dev)
-        nv.call("ic2_gumbel_softmax_quantize_bwd", nv.ptr(zf), m, nv.ptr(codebook), k, nv.ptr(logt), 1.0,
-                nv.ptr(seed), 0, nv.ptr(gumbel_noise), nv.ptr(g), nv.ptr(q), nv.ptr(dz), nv.ptr(dlogt), nv.ptr(ws),
-                nbytes, nv.stream_of(zf))
+        dz, dlogt = ops.gumbel_quantize_bwd(zf, codebook, logt, seed, gumbel_noise, g, q, ctx.needs_input_grad[1])
         if dlogt is not None:
             dlogt = dlogt.view(logt.shape).to(logt.dtype)
         dz = dz.view(ctx.z_shape).to(ctx.z_dtype) if ctx.needs_input_grad[0] else None
@@ -333,7 +271,6 @@ def _synth_layer_grads(L, dt, os_, y, dout, post=None):
     not mix channels), so the multiply rides on its per-channel output multiplier: dc = FLRbwd(dout) * oscale * post,
     and the ydot partials (taken against that multiplier) give dL/doscale = post * sum / oscale."""
     n, h, w, c_p = y.shape
-    stream = nv.stream_of(y)
     _, _, bp = L.packed(dt)
     fu, fd = L._fu, L._fd
     px0, px1, py0, py1 = L.padding
@@ -347,21 +284,12 @@ def _synth_layer_grads(L, dt, os_, y, dout, post=None):
     # test_wino_dgrad_overflows_at_the_direct_gemms_scale).  Storing dc halved against 2 U would remove the V hazard
     # but costs a bit on every f16-subnormal dc value (a 2^12 loss scale's synthesis gradient: 3.06e-2 vs < 3e-2
     # relative error), so dc is stored as is.
-    rc = 2
+    fused = False
     if fu is not None and fd is not None and px0 == py0:
         # a radial layer's 2-D down filter [12][12]: the 2-D kernel, with its own ydot tiling
-        fn = "ic2_flrelu_bwd_nhwc_2d" if L.down_radial else "ic2_flrelu_bwd_nhwc_ex"
-        nyd = int(nv.query("ic2_flrelu_bwd_2d_ydot_floats" if L.down_radial else "ic2_flrelu_bwd_ydot_floats", n, c_p,
-                           h, w, L.up_factor))
-        ydot = torch.empty([nyd], dtype=torch.float32, device=y.device)
-        rc = getattr(nv.load(), fn)(
-            nv.ptr(y), nv.dtype_code(y.dtype), nv.ptr(dout), nv.dtype_code(dout.dtype), nv.ptr(dc),
-            nv.dtype_code(dt), n, c_p, h, w, dout.shape[1], dout.shape[2], fu.ctypes.data_as(ctypes.c_void_p),
-            fu.shape[0], fd.ctypes.data_as(ctypes.c_void_p), fd.shape[0], L.up_factor, L.down_factor, px0, px1,
-            py0, py1, float(L.act_gain), 0.2, clamp, 0, nv.ptr(mul), nv.ptr(bp), nv.ptr(ydot), nyd, stream)
-        if rc not in (0, 2):
-            raise RuntimeError(f"{fn} failed: {nv.load().ic2_last_error().decode()}")
-    if rc == 0:   # dL/doscale = sum over tiles of the ydot partials / oscale (0 where oscale is 0), one launch
+        fused, ydot = ops.flrelu_bwd(y, dout, dc, n, c_p, h, w, fu, fd, L.up_factor, L.down_factor, L.padding,
+                                     L.act_gain, 0.2, clamp, radial=L.down_radial, store=True, mul=mul, bias=bp)
+    if fused:   # dL/doscale = sum over tiles of the ydot partials / oscale (0 where oscale is 0), one launch
         d_os = nv.colsum_div(ydot, n, c_p, os32)
         if post is not None:
             d_os = d_os * post
@@ -385,16 +313,9 @@ def _synth_conv_fwd(layer, a, os_, dt, y):
     n, s_in = a.shape[0], a.shape[1]
     k = layer.conv_kernel
     pad = k - 1
-    conv = y.shape[1]
     wp, _, bp = layer.packed(dt)
-    if dt == torch.float16 and nv.wino_preferred(nv.F16, n, s_in, s_in, layer.cin_p, layer.cout_p, k, k, pad):
-        nv.conv_wino(nv.ptr(a), nv.ptr(layer.packed_wino()), nv.ptr(y), nv.F16, nv.dtype_code(y.dtype), n, s_in, s_in,
-                     layer.cin_p, layer.cout_p, layer.out_channels, pad, conv, conv, nv.ptr(os_), nv.ptr(bp), 0, 0.0,
-                     1.0, -1.0, 1.0, nv.NHWC, nv.stream_of(a))
-        return
-    nv.conv_igemm(nv.ptr(a), nv.ptr(wp), nv.ptr(y), nv.dtype_code(dt), nv.dtype_code(y.dtype), n, s_in, s_in,
-                  layer.cin_p, layer.cout_p, layer.out_channels, k, k, pad, conv, conv, nv.ptr(os_), nv.ptr(bp), 0,
-                  0.0, 1.0, -1.0, 1.0, nv.NHWC, nv.stream_of(a), a.device)
+    ops.conv(a, wp, y, nv.dtype_code(dt), n, s_in, s_in, layer.cin_p, layer.cout_p, layer.out_channels, k, pad,
+             oscale=os_, bias=bp, wino=layer.packed_wino if dt == torch.float16 else None)
 
 
 class SynthLayerScaledNHWC(torch.autograd.Function):
@@ -429,12 +350,9 @@ class SynthLayerScaledNHWC(torch.autograd.Function):
         L, dt = ctx.layer, ctx.dt
         g = g.to(out.dtype).contiguous()
         n, ho, wo, c_p = out.shape
-        npart = int(nv.query("ic2_scale_bwd_part_floats", n, ho * wo, c_p))
-        part = torch.empty([npart], dtype=torch.float32, device=out.device)
-        # the sums for d xs_next only: g * xs_next itself rides on the FLR backward's output multiplier (post=)
-        nv.call("ic2_scale_bwd_nhwc", nv.ptr(g), nv.ptr(out), nv.ptr(xs), None, nv.dtype_code(out.dtype), n,
-                ho * wo, c_p, nv.ptr(part), npart, nv.stream_of(out))
-        d_xs = nv.colsum_div(part, n, c_p, xs)   # sum_p g * out / xs_next, 0 where xs_next = 0
+        # the sums for d xs_next only (sum_p g * out / xs_next, 0 where xs_next = 0): g * xs_next itself rides on the
+        # FLR backward's output multiplier (post=)
+        _, d_xs = ops.scale_bwd(g, out, xs, n, ho * wo, c_p, want_dx=False, div=True)
         da, d_os = _synth_layer_grads(L, dt, os_, y, g, post=xs)
         return da, d_os, d_xs, None, None
 
@@ -449,9 +367,7 @@ class ScaleNHWC(torch.autograd.Function):
         x = x.contiguous()
         n, h, w, c_p = x.shape
         xs32 = xs.detach().float().contiguous()
-        a = torch.empty_like(x)
-        nv.call("ic2_scale_nhwc", nv.ptr(x), nv.ptr(xs32), nv.ptr(a), nv.dtype_code(x.dtype), n, h * w, c_p,
-                nv.stream_of(x))
+        a = ops.scale(x, xs32, n, h * w, c_p)
         ctx.save_for_backward(x, xs32)
         return a
 
@@ -459,13 +375,7 @@ class ScaleNHWC(torch.autograd.Function):
     def backward(ctx, da):
         x, xs = ctx.saved_tensors
         n, h, w, c_p = x.shape
-        da = da.to(x.dtype).contiguous()
-        npart = int(nv.query("ic2_scale_bwd_part_floats", n, h * w, c_p))
-        part = torch.empty([npart], dtype=torch.float32, device=x.device)
-        dx = torch.empty_like(x)
-        nv.call("ic2_scale_bwd_nhwc", nv.ptr(da), nv.ptr(x), nv.ptr(xs), nv.ptr(dx), nv.dtype_code(x.dtype), n, h * w,
-                c_p, nv.ptr(part), npart, nv.stream_of(x))
-        return dx, nv.colsum_div(part, n, c_p)
+        return ops.scale_bwd(da.to(x.dtype).contiguous(), x, xs, n, h * w, c_p)
 
 
 class FrozenConvNHWC(torch.autograd.Function):
@@ -520,29 +430,12 @@ class FilteredLReluNHWC(torch.autograd.Function):
         fu, fd = L._fu, L._fd
         px0, px1, py0, py1 = L.padding
         clamp = float(L.conv_clamp) if L.conv_clamp is not None else -1.0
-        if L.down_radial and fu is not None and fd is not None and px0 == py0:
-            # the 2-D kernel's (f32, f32, f32) / (f16, f32, f32) instances; other gradient dtypes compose
+        if fu is not None and fd is not None and px0 == py0:
+            # radial: the 2-D kernel's (f32, f32, f32) / (f16, f32, f32) instances; other gradient dtypes compose
             dy = torch.empty([n, h, w, c_p], dtype=torch.float32, device=y.device)
-            rc = nv.load().ic2_flrelu_bwd_nhwc_2d(
-                nv.ptr(y), nv.dtype_code(y.dtype), nv.ptr(dout), nv.dtype_code(dout.dtype), nv.ptr(dy), nv.F32, n, c_p, h,
-                w, dout.shape[1], dout.shape[2], fu.ctypes.data_as(ctypes.c_void_p), fu.shape[0],
-                fd.ctypes.data_as(ctypes.c_void_p), fd.shape[0], L.up_factor, L.down_factor, px0, px1, py0, py1,
-                float(L.act_gain), 0.2, clamp, 0, None, None, None, 0, nv.stream_of(y))
-            if rc == 0:
+            if ops.flrelu_bwd(y, dout, dy, n, c_p, h, w, fu, fd, L.up_factor, L.down_factor, L.padding, L.act_gain, 0.2,
+                              clamp, radial=L.down_radial)[0]:
                 return dy, None, None
-            if rc != 2:
-                raise RuntimeError(f"ic2_flrelu_bwd_nhwc_2d failed: {nv.load().ic2_last_error().decode()}")
-        elif fu is not None and fd is not None and px0 == py0:
-            dy = torch.empty([n, h, w, c_p], dtype=torch.float32, device=y.device)
-            rc = nv.load().ic2_flrelu_bwd_nhwc(
-                nv.ptr(y), nv.dtype_code(y.dtype), nv.ptr(dout), nv.dtype_code(dout.dtype), nv.ptr(dy), n, c_p, h, w,
-                dout.shape[1], dout.shape[2], fu.ctypes.data_as(ctypes.c_void_p), fu.shape[0],
-                fd.ctypes.data_as(ctypes.c_void_p), fd.shape[0], L.up_factor, L.down_factor, px0, px1, py0, py1,
-                float(L.act_gain), 0.2, clamp, 0, nv.stream_of(y))
-            if rc == 0:
-                return dy, None, None
-            if rc != 2:   # anything but IC2_E_UNSUPPORTED is an error
-                raise RuntimeError(f"ic2_flrelu_bwd_nhwc failed: {nv.load().ic2_last_error().decode()}")
         return _flrelu_backward_composed(y, dout, L), None, None
 
 
@@ -581,9 +474,7 @@ class SynthLayerNHWC(torch.autograd.Function):
         x = x.contiguous()
         xs32 = xs.detach().float().contiguous()
         assert xs32.shape == (n, x.shape[3]), (xs32.shape, x.shape)
-        a = torch.empty_like(x)
-        nv.call("ic2_scale_nhwc", nv.ptr(x), nv.ptr(xs32), nv.ptr(a), nv.dtype_code(x.dtype), n, s_in * s_in,
-                x.shape[3], nv.stream_of(x))
+        a = ops.scale(x, xs32, n, s_in * s_in, x.shape[3])
         k = layer.conv_kernel
         pad = k - 1
         conv = s_in + 2 * pad - k + 1
@@ -601,10 +492,5 @@ class SynthLayerNHWC(torch.autograd.Function):
         x, xs, os_, y = ctx.saved_tensors
         da, d_os = _synth_layer_grads(ctx.layer, ctx.dt, os_, y, dout.contiguous())
         n, hi, wi, cin_p = x.shape
-        npart = int(nv.query("ic2_scale_bwd_part_floats", n, hi * wi, cin_p))
-        part = torch.empty([npart], dtype=torch.float32, device=x.device)
-        dx = torch.empty_like(x)
-        nv.call("ic2_scale_bwd_nhwc", nv.ptr(da), nv.ptr(x), nv.ptr(xs), nv.ptr(dx), nv.dtype_code(x.dtype), n, hi * wi,
-                cin_p, nv.ptr(part), npart, nv.stream_of(y))
-        d_xs = nv.colsum_div(part, n, cin_p)
+        dx, d_xs = ops.scale_bwd(da, x, xs, n, hi * wi, cin_p)
         return dx, d_xs, d_os, None, None

@@ -30,9 +30,6 @@ conv / filtered-lrelu kernels with HIP backward passes (autograd_ops), gradients
 """
 from __future__ import annotations
 
-import ctypes
-import math
-
 import numpy as np
 import scipy.signal
 import scipy.special
@@ -41,6 +38,7 @@ import torch.nn.functional as F
 
 from . import _native as nv
 from . import autograd_ops as ao
+from . import ops
 from . import sg3_ops
 
 # conv -> filtered lrelu hand-off in the channel-blocked NHWC16 layout (bf16 mode); knob IC2_FLR_BLOCKED=0 (IC2_DEV=1):
@@ -133,13 +131,9 @@ class FullyConnectedLayer(torch.nn.Module):
         """x: f32 [n, ldx] rows (only the first in_features of each row are read)."""
         n = x.shape[0] if n is None else n
         ldx = self.in_features if ldx is None else ldx
-        if out is None:
-            out = torch.empty([n, self.out_features], dtype=torch.float32, device=x.device)
         act = nv.ACT_LRELU if self.activation == "lrelu" else nv.ACT_LINEAR
-        nv.call("ic2_fc", nv.ptr(x), ldx, nv.ptr(self.weight), nv.ptr(self.bias), nv.ptr(out), n, self.in_features,
-                self.out_features, float(self.weight_gain), float(self.bias_gain), act, 0.2,
-                float(np.sqrt(2)) if act == nv.ACT_LRELU else 1.0, nv.stream_of(x))
-        return out
+        return ops.fc(x, ldx, self.weight, self.bias, n, self.in_features, self.out_features, w_gain=self.weight_gain,
+                      b_gain=self.bias_gain, act=act, act_gain=np.sqrt(2) if act == nv.ACT_LRELU else 1.0, out=out)
 
     def forward(self, x):
         xin = x
@@ -213,10 +207,7 @@ class SynthesisInput(torch.nn.Module):
         if hit is not None and hit[0] == key:
             return hit[1]
         C, cp = self.channels, nv.pad_synth(self.channels)
-        w = self.weight.detach().to(torch.float32).contiguous()
-        out = torch.empty([cp, cp], dtype=dt, device=w.device)
-        nv.call("ic2_pack_weight", nv.ptr(w), C, C, 1, 1, cp, cp, 0, float(1 / np.sqrt(C)), nv.ptr(out),
-                nv.dtype_code(dt), None, nv.stream_of(w))
+        out = ops.pack_weight(self.weight, cp, cp, dt, scale=1 / np.sqrt(C))
         self._cache[dt] = (key, out)
         return out
 
@@ -225,17 +216,11 @@ class SynthesisInput(torch.nn.Module):
         C, cp, S = self.channels, nv.pad_synth(self.channels), int(self.size[0])
         dev = ws.device
         t = self.affine.run(ws, ldx=ldx, n=n)
-        feats = torch.empty([n, S, S, cp], dtype=dt, device=dev)
-        nv.call("ic2_synth_input_features", nv.ptr(t), nv.ptr(self.freqs), nv.ptr(self.phases), nv.ptr(self.transform),
-                n, C, cp, S, float(self.sampling_rate), float(self.bandwidth), nv.ptr(feats), nv.dtype_code(dt),
-                nv.stream_of(ws))
+        feats = ops.synth_input_features(t, self.freqs, self.phases, self.transform, n, C, cp, S, self.sampling_rate,
+                                         self.bandwidth, dt)
         out = torch.empty([n, S, S, cp], dtype=dt, device=dev)
-        w = self.packed_weight(dt)
-        nv.note_flops(2 * n * S * S * C * C)
-        nv.conv_igemm(nv.ptr(feats), nv.ptr(w), nv.ptr(out), nv.dtype_code(dt), nv.dtype_code(dt), n, S, S, cp, cp, C,
-                      1, 1, 0, S, S, nv.ptr(post_scale), None, 0, 0.0, 1.0, -1.0, 1.0, nv.NHWC, nv.stream_of(ws),
-                      feats.device)
-        return out
+        return ops.conv(feats, self.packed_weight(dt), out, nv.dtype_code(dt), n, S, S, cp, cp, C, 1, 0,
+                        oscale=post_scale, flops=2 * n * S * S * C * C)
 
     def _train_grid(self, device):
         """The sampling grid of the Fourier features (constant): built once per device.  Built on every call, its
@@ -284,9 +269,7 @@ class SynthesisInput(torch.nn.Module):
         nv.require_gpu(w)
         n, S, C, cp = w.shape[0], int(self.size[0]), self.channels, nv.pad_synth(self.channels)
         x = self.run_nhwc(w, self.w_dim, n, torch.float32, None)
-        y = torch.empty([n, C, S, S], dtype=torch.float32, device=w.device)
-        nv.call("ic2_nhwc_to_nchw", nv.ptr(x), nv.F32, nv.ptr(y), n, C, S, S, cp, nv.stream_of(w))
-        return _refuse(self, y, w_in)
+        return _refuse(self, ops.to_nchw(x, n, C, S, S, cp), w_in)
 
     def extra_repr(self):
         return (f"w_dim={self.w_dim:d}, channels={self.channels:d}, size={list(self.size)}, "
@@ -379,13 +362,8 @@ class SynthesisLayer(torch.nn.Module):
         hit = self._cache.get(dt)
         if hit is not None and hit[0] == key:
             return hit[1]
-        w = self.weight.detach().to(torch.float32).contiguous()
-        k = self.conv_kernel
-        wp = torch.empty([self.cout_p, k, k, self.cin_p], dtype=dt, device=w.device)
-        wsq = torch.empty([self.out_channels, self.in_channels], dtype=torch.float32, device=w.device)
-        nv.call("ic2_pack_weight", nv.ptr(w), self.out_channels, self.in_channels, k, k, self.cout_p, self.cin_p,
-                int(not self.is_torgb), 1.0, nv.ptr(wp), nv.dtype_code(dt), nv.ptr(wsq), nv.stream_of(w))
-        bp = torch.zeros([self.cout_p], dtype=torch.float32, device=w.device)
+        wp, wsq = ops.pack_weight(self.weight, self.cout_p, self.cin_p, dt, prenorm=not self.is_torgb, wsq=True)
+        bp = torch.zeros([self.cout_p], dtype=torch.float32, device=wp.device)
         bp[: self.out_channels] = self.bias.detach().float()
         val = (wp, wsq, bp)
         self._cache[dt] = (key, val)
@@ -418,17 +396,14 @@ class SynthesisLayer(torch.nn.Module):
         if unbatched or not self.batchable():
             _, wsq, _ = self.packed(dt)
             fc = self.affine
-            stream = nv.stream_of(ws)
-            nv.call("ic2_fc", nv.ptr(ws), ldx, nv.ptr(fc.weight), nv.ptr(fc.bias), nv.ptr(styles), n, fc.in_features,
-                    self.in_channels, float(fc.weight_gain), float(fc.bias_gain), nv.ACT_LINEAR, 0.0, 1.0, stream)
+            ops.fc(ws, ldx, fc.weight, fc.bias, n, fc.in_features, self.in_channels, w_gain=fc.weight_gain,
+                   b_gain=fc.bias_gain, alpha=0.0, out=styles)
             style_gain = float(1 / np.sqrt(self.in_channels * (self.conv_kernel ** 2))) if self.is_torgb else 1.0
-            nv.call("ic2_modconv_prep", nv.ptr(styles), nv.ptr(wsq), n, self.in_channels, self.out_channels,
-                    self.cin_p, self.cout_p, int(not self.is_torgb), style_gain, float(self.input_gain()), nv.ptr(xs),
-                    nv.ptr(os_), None, stream)
+            ops.modconv_prep(styles, wsq, n, self.in_channels, self.out_channels, self.cin_p, self.cout_p,
+                             not self.is_torgb, style_gain, self.input_gain(), xs, os_)
             return xs, os_
         rec = np.asarray([self.mod_record(dt, 0, styles, xs, os_)], dtype=np.int64)
-        nv.call("ic2_modconv_prep_batched", nv.ptr(ws), ldx, n, self.affine.in_features, 1,
-                rec.ctypes.data_as(ctypes.c_void_p), nv.stream_of(ws))
+        ops.modconv_prep_batched(ws, ldx, n, self.affine.in_features, rec)
         return xs, os_
 
     # ---- NHWC pipeline step ------------------------------------------------------------------
@@ -485,31 +460,27 @@ class SynthesisLayer(torch.nn.Module):
         pad = k - 1
         conv = s_in + 2 * pad - k + 1
         wp, _, bp = self.packed(dt)
-        stream = nv.stream_of(x)
-        nv.note_flops(2 * n * conv * conv * self.out_channels * self.in_channels * k * k)
-        in_flag = nv.act_in_layout(nv.NHWC16) if x_blocked else 0  # the input layout rides above the conv's `act`
+        flops = 2 * n * conv * conv * self.out_channels * self.in_channels * k * k
         if self.is_torgb:
             assert self.up_factor == 1 and self.down_factor == 1 and self.padding == [0, 0, 0, 0] and trim is None
             out = torch.empty([n, self.out_channels, conv, conv], dtype=torch.float32, device=x.device)
             clamp = float(self.conv_clamp) if self.conv_clamp is not None else -1.0
-            nv.conv_igemm(nv.ptr(x), nv.ptr(wp), nv.ptr(out), nv.dtype_code(dt), nv.F32, n, s_in, s_in, self.cin_p,
-                          self.cout_p, self.out_channels, k, k, pad, conv, conv, nv.ptr(oscale), nv.ptr(bp),
-                          nv.ACT_LRELU | in_flag, 1.0, 1.0, clamp,
-                          float(1.0 if final_scale is None else final_scale), nv.NCHW, stream, x.device)
-            return out
-        y, blocked = self.conv_nhwc(x, n, dt, oscale, x_blocked=x_blocked, trim=trim)
+            return ops.conv(x, wp, out, nv.dtype_code(dt), n, s_in, s_in, self.cin_p, self.cout_p, self.out_channels, k,
+                            pad, oscale=oscale, bias=bp, act=nv.ACT_LRELU, slope=1.0, clamp=clamp,
+                            in_layout=nv.NHWC16 if x_blocked else nv.NHWC, out_layout=nv.NCHW, flops=flops,
+                            out_mul=float(1.0 if final_scale is None else final_scale))
+        y, blocked = self.conv_nhwc(x, n, dt, oscale, x_blocked=x_blocked, trim=trim, flops=flops)
         return self.flrelu_nhwc(y, dt, post_scale, blocked=blocked, out_blocked=out_blocked, trim=trim)
 
-    def conv_nhwc(self, x, n, dt, oscale, x_blocked=False, trim=None):
+    def conv_nhwc(self, x, n, dt, oscale, x_blocked=False, trim=None, flops=None):
         """The modulated conv of a non-ToRGB layer (x_blocked: the input is channel-blocked, for a layer whose
         takes_blocked_input is true): -> (conv output y, blocked layout?) for flrelu_nhwc.  trim: the conv runs with
-        the padding trim.conv_pad, y is that much smaller."""
+        the padding trim.conv_pad, y is that much smaller.  flops: the algorithmic FLOPs to announce (run_nhwc's)."""
         s_in = int(self.in_size[0])
         k = self.conv_kernel
         pad = k - 1 if trim is None else trim.conv_pad
         conv = s_in + 2 * pad - k + 1
         wp, _, bp = self.packed(dt)
-        stream = nv.stream_of(x)
         # bf16 / f16 mode: the conv output feeds the MFMA filtered-lrelu, whose operands are f16 -> store it as f16, in
         # the channel-blocked layout [n][cout_p/16][conv][conv][16] the fused kernel's 16-channel tiles read as
         # contiguous rows (IC2_FLR_BLOCKED=0: plain NHWC)
@@ -519,17 +490,10 @@ class SynthesisLayer(torch.nn.Module):
             y = torch.empty([n, self.cout_p // 16, conv, conv, 16], dtype=ydt, device=x.device)
         else:
             y = torch.empty([n, conv, conv, self.cout_p], dtype=ydt, device=x.device)
-        layout = nv.NHWC16 if blocked else nv.NHWC
-        in_flag = nv.act_in_layout(nv.NHWC16) if x_blocked else 0  # the input layout rides above the conv's `act`
-        if nv.wino_preferred(nv.dtype_code(dt), n, s_in, s_in, self.cin_p, self.cout_p, k, k, pad):
-            # f16, >= 256 channels: the fused Winograd F(2,3)-along-x kernel (2/3 of the MFMA work, wino.hip)
-            nv.conv_wino(nv.ptr(x), nv.ptr(self.packed_wino()), nv.ptr(y), nv.F16, nv.dtype_code(ydt), n, s_in, s_in,
-                         self.cin_p, self.cout_p, self.out_channels, pad, conv, conv, nv.ptr(oscale), nv.ptr(bp),
-                         in_flag, 0.0, 1.0, -1.0, 1.0, layout, stream)
-        else:
-            nv.conv_igemm(nv.ptr(x), nv.ptr(wp), nv.ptr(y), nv.dtype_code(dt), nv.dtype_code(ydt), n, s_in, s_in,
-                          self.cin_p, self.cout_p, self.out_channels, k, k, pad, conv, conv, nv.ptr(oscale),
-                          nv.ptr(bp), in_flag, 0.0, 1.0, -1.0, 1.0, layout, stream, x.device)
+        # wino: f16, >= 256 channels run the fused Winograd F(2,3)-along-x kernel (2/3 of the MFMA work, wino.hip)
+        ops.conv(x, wp, y, nv.dtype_code(dt), n, s_in, s_in, self.cin_p, self.cout_p, self.out_channels, k, pad,
+                 oscale=oscale, bias=bp, in_layout=nv.NHWC16 if x_blocked else nv.NHWC,
+                 out_layout=nv.NHWC16 if blocked else nv.NHWC, wino=self.packed_wino, flops=flops)
         return y, blocked
 
     def packed_wino(self):
@@ -539,10 +503,7 @@ class SynthesisLayer(torch.nn.Module):
         hit = self._cache.get("wino")
         if hit is not None and hit[0] == key:
             return hit[1]
-        w = self.weight.detach().to(torch.float32).contiguous()
-        u = torch.empty([self.cout_p, 3, 4, self.cin_p], dtype=torch.float16, device=w.device)
-        nv.call("ic2_pack_weight_wino", nv.ptr(w), self.out_channels, self.in_channels, self.cout_p, self.cin_p,
-                int(not self.is_torgb), 1.0, nv.ptr(u), nv.F16, nv.stream_of(w))
+        u = ops.pack_weight_wino(self.weight, self.cout_p, self.cin_p, prenorm=not self.is_torgb)
         self._cache["wino"] = (key, u)
         return u
 
@@ -557,25 +518,11 @@ class SynthesisLayer(torch.nn.Module):
             out = torch.empty([n, self.cout_p // 16, s_out, s_out, 16], dtype=dt_out, device=y.device)
         else:
             out = torch.empty([n, s_out, s_out, self.cout_p], dtype=dt_out, device=y.device)
-        fu = self._fu
-        fd = self._fd
-        px0, px1, py0, py1 = self.padding if trim is None else trim.flr_padding
         clamp = float(self.conv_clamp) if self.conv_clamp is not None else -1.0
-        if self.down_radial:
-            fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-            nv.call("ic2_flrelu_nhwc16_2d" if blocked else "ic2_flrelu_nhwc_2d", nv.ptr(y), nv.ptr(out),
-                    nv.dtype_code(y.dtype), nv.dtype_code(dt_out) | (nv.flr_out_layout(nv.NHWC16) if out_blocked else 0),
-                    n, self.cout_p, conv, conv, s_out, s_out, fp(fu), 1 if fu is None else fu.shape[0], fp(fd),
-                    fd.shape[0], self.down_rank, fp(self._fdv), fp(self._fdh), None, self.up_factor, self.down_factor,
-                    px0, px1, py0, py1, float(self.act_gain), 0.2, clamp, 0, nv.ptr(post_scale), nv.stream_of(y))
-            return out
-        nv.call("ic2_flrelu_nhwc16" if blocked else "ic2_flrelu_nhwc", nv.ptr(y), nv.ptr(out), nv.dtype_code(y.dtype),
-                nv.dtype_code(dt_out) | (nv.flr_out_layout(nv.NHWC16) if out_blocked else 0), n,
-                self.cout_p, conv, conv, s_out, s_out, None if fu is None else fu.ctypes.data_as(ctypes.c_void_p),
-                1 if fu is None else fu.shape[0], None if fd is None else fd.ctypes.data_as(ctypes.c_void_p),
-                1 if fd is None else fd.shape[0], None, self.up_factor, self.down_factor, px0, px1, py0, py1,
-                float(self.act_gain), 0.2, clamp, 0, nv.ptr(post_scale), nv.stream_of(y))
-        return out
+        return ops.flrelu(y, out, n, self.cout_p, conv, s_out, self._fu, self._fd, self.up_factor, self.down_factor,
+                          self.padding if trim is None else trim.flr_padding, self.act_gain, 0.2, clamp,
+                          post_scale=post_scale, blocked=blocked, out_blocked=out_blocked,
+                          radial=(self.down_rank, self._fdv, self._fdh) if self.down_radial else None)
 
     # ---- autograd path: gradients w.r.t. the input activation and w (weights frozen) ----------------------
     def packed_adjoint(self, dt):
@@ -602,10 +549,7 @@ class SynthesisLayer(torch.nn.Module):
         w = self.weight.detach().to(torch.float32)
         if not self.is_torgb:
             w = w * w.square().mean(dim=[1, 2, 3], keepdim=True).rsqrt()
-        wa = w.transpose(0, 1).flip(2, 3).contiguous()
-        u = torch.empty([self.cin_p, 3, 4, self.cout_p], dtype=torch.float16, device=w.device)
-        nv.call("ic2_pack_weight_wino", nv.ptr(wa), self.in_channels, self.out_channels, self.cin_p, self.cout_p, 0,
-                float(scale), nv.ptr(u), nv.F16, nv.stream_of(wa))
+        u = ops.pack_weight_wino(w.transpose(0, 1).flip(2, 3), self.cin_p, self.cout_p, scale=scale)
         self._cache[("adj_wino", scale)] = (key, u)
         return u
 
@@ -663,18 +607,11 @@ class SynthesisLayer(torch.nn.Module):
         assert list(x.shape) == [n, self.in_channels, int(self.in_size[1]), int(self.in_size[0])], x.shape
         dt = torch.float32
         xs, os_ = self.scales(w, self.w_dim, n, dt)
-        s_in = int(self.in_size[0])
-        xn = torch.empty([n, s_in, s_in, self.cin_p], dtype=dt, device=x.device)
-        nv.call("ic2_nchw_to_nhwc", nv.ptr(x), nv.ptr(xn), nv.F32, n, self.in_channels, s_in, s_in, self.cin_p,
-                nv.ptr(xs), nv.stream_of(x))
-        out = self.run_nhwc(xn, n, dt, os_, None)
+        out = self.run_nhwc(ops.to_nhwc(x, dt, self.cin_p, scale=xs), n, dt, os_, None)
         if self.is_torgb:
             return _refuse(self, out, x_in, w_in)
         s_out = int(self.out_size[0])
-        y = torch.empty([n, self.out_channels, s_out, s_out], dtype=torch.float32, device=x.device)
-        nv.call("ic2_nhwc_to_nchw", nv.ptr(out), nv.F32, nv.ptr(y), n, self.out_channels, s_out, s_out, self.cout_p,
-                nv.stream_of(x))
-        return _refuse(self, y, x_in, w_in)
+        return _refuse(self, ops.to_nchw(out, n, self.out_channels, s_out, s_out, self.cout_p), x_in, w_in)
 
     def forward_train(self, x, w):
         """Layer-level autograd path (NCHW f32 in/out), fp32."""
@@ -851,8 +788,7 @@ class SynthesisNetwork(torch.nn.Module):
             off += sizes[i]
             rec[i] = L.mod_record(dt, (i + 1) * self.w_dim, styles, xs, os_)
             out.append((xs, os_))
-        nv.call("ic2_modconv_prep_batched", nv.ptr(ws), ldx, n, self.w_dim, len(layers),
-                rec.ctypes.data_as(ctypes.c_void_p), nv.stream_of(ws))
+        ops.modconv_prep_batched(ws, ldx, n, self.w_dim, rec)
         return out
 
     def _train_mod_pack(self, convs, device):

@@ -122,14 +122,11 @@ def _filtered_lrelu_fwd(x, fu=None, fd=None, b=None, up=1, down=1, padding=0, ga
         gu = _host_taps(fu)
         gd = _host_taps(fd)
         y = torch.empty([n, c, oh, ow], dtype=x.dtype, device=x.device)
-        lib = nv.load()
-        rc = lib.ic2_filtered_lrelu(nv.ptr(x), nv.ptr(y), nv.dtype_code(x.dtype), n, c, h, w, oh, ow, gu[0], gu[1], gd[0],
-                                    gd[1], nv.ptr(b), int(up), int(down), px0, px1, py0, py1, float(gain), float(slope),
-                                    float(clamp if clamp is not None else -1), int(bool(flip_filter)), nv.stream_of(x))
-        if rc == 0:
+        if nv.try_call("ic2_filtered_lrelu", nv.ptr(x), nv.ptr(y), nv.dtype_code(x.dtype), n, c, h, w, oh, ow, gu[0],
+                       gu[1], gd[0], gd[1], nv.ptr(b), int(up), int(down), px0, px1, py0, py1, float(gain),
+                       float(slope), float(clamp if clamp is not None else -1), int(bool(flip_filter)),
+                       nv.stream_of(x)):
             return y
-        if rc != 2:  # anything but IC2_E_UNSUPPORTED is an error
-            raise RuntimeError(f"ic2_filtered_lrelu failed: {lib.ic2_last_error().decode()}")
     # composition of the reference's four steps, each a HIP kernel
     t = _bias_act_fwd(x, b)
     t = _upfirdn2d_fwd(t, fu, up=up, padding=[px0, px1, py0, py1], gain=up ** 2, flip_filter=flip_filter)

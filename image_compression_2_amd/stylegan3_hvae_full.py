@@ -28,6 +28,7 @@ from PIL import Image
 
 from . import _native as nv
 from . import autograd_ops as ao
+from . import ops
 
 
 def _version_key(*tensors):
@@ -62,6 +63,12 @@ class _Act:
         return nv.BF16X3 if self.x3 else nv.F16X2 if self.h2 else nv.dtype_code(self.t.dtype)
 
 
+# The `stream` parameter of the helpers and methods below is unused: ops asks for the current stream of the tensor's
+# device at each launch (which is what every caller passed).  It stays only because the GPU tests call these helpers
+# with that signature; the module itself passes None.
+_NO_STREAM = None
+
+
 def _packed(conv: nn.Conv2d, x: _Act, dt, cache: dict, stream):
     cout, cin, kh, kw = conv.weight.shape
     assert conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and cin == x.c
@@ -76,14 +83,11 @@ def _packed(conv: nn.Conv2d, x: _Act, dt, cache: dict, stream):
         # the low halves of all but the ~2^-15-smallest weights stay f16 normals), the conv output times 2^-s (exact)
         mul = 1.0
         if h2:
-            wp = torch.empty([cout_p, kh, kw, 2 * cin_p], dtype=torch.float16, device=w.device)
             m = float(w.abs().max().item())
             sh = 13 - math.frexp(m)[1] if m > 0 else 0
             mul = math.ldexp(1.0, -sh)
-        else:
-            wp = torch.empty([cout_p, kh, kw, 3 * cin_p if x3 else cin_p], dtype=dt, device=w.device)
-        nv.call("ic2_pack_weight", nv.ptr(w), cout, cin, kh, kw, cout_p, cin_p, 0, 1.0 / mul, nv.ptr(wp),
-                nv.BF16X3 if x3 else nv.F16X2 if h2 else nv.dtype_code(dt), None, stream)
+        wp = ops.pack_weight(w, cout_p, cin_p, torch.float16 if h2 else dt, scale=1.0 / mul,
+                             code=nv.BF16X3 if x3 else nv.F16X2 if h2 else None)
         bp = torch.zeros([cout_p], dtype=torch.float32, device=w.device)
         if conv.bias is not None:
             bp[:cout] = conv.bias.detach().float() / mul
@@ -112,10 +116,8 @@ def _conv(conv: nn.Conv2d, x: _Act, dt, cache: dict, stream):
     cout_p = wp.shape[0]
     ho, wo = x.h + 2 * pad - kh + 1, x.w + 2 * pad - kw + 1
     y = torch.empty([x.n, ho, wo, cout_p], dtype=dt, device=x.t.device)
-    nv.note_flops(_conv_flops(x.n, ho, wo, cout, cin, kh, kw))
-    nv.conv_igemm(nv.ptr(x.t), nv.ptr(wp), nv.ptr(y), nv.dtype_code(x.t.dtype), nv.dtype_code(dt), x.n, x.h, x.w,
-                  x.c_p, cout_p, cout, kh, kw, pad, ho, wo, None, nv.ptr(bp), 0, 0.0, 1.0, -1.0, 1.0, nv.NHWC, stream,
-                  x.t.device)
+    ops.conv(x.t, wp, y, nv.dtype_code(x.t.dtype), x.n, x.h, x.w, x.c_p, cout_p, cout, (kh, kw), pad, bias=bp,
+             flops=_conv_flops(x.n, ho, wo, cout, cin, kh, kw))
     return _Act(y, cout)
 
 
@@ -142,27 +144,23 @@ def _from_rgb(conv: nn.Conv2d, x, dt, cache: dict, stream, split=False, h2=False
         if h2 and direct:
             y = torch.empty([n, hh, ww, cout_p], dtype=torch.float16, device=x.device)
             wf = conv.weight.detach().to(torch.float32).contiguous()
-            nv.note_flops(_conv_flops(n, hh, ww, cout, cin, 3, 3))
-            nv.call("ic2_from_rgb_conv_f16", nv.ptr(x), cin, nv.ptr(wf), cout, nv.ptr(bp), nv.ptr(y), n, hh, ww,
-                    cout_p, stream)
+            ops.from_rgb_conv("f16", x, wf, bp, y, n, hh, ww, cin, cout, cout_p,
+                              flops=_conv_flops(n, hh, ww, cout, cin, 3, 3))
             return _Act(y, cout, h2=True)
         y = torch.empty([n, hh, ww, 2 * cout_p], dtype=torch.bfloat16, device=x.device)
         if direct:
             wf = conv.weight.detach().to(torch.float32).contiguous()
-            nv.note_flops(_conv_flops(n, hh, ww, cout, cin, 3, 3))
-            nv.call("ic2_from_rgb_conv_x3", nv.ptr(x), cin, nv.ptr(wf), cout, nv.ptr(bp), nv.ptr(y), n, hh, ww, cout_p,
-                    stream)
+            ops.from_rgb_conv("x3", x, wf, bp, y, n, hh, ww, cin, cout, cout_p,
+                              flops=_conv_flops(n, hh, ww, cout, cin, 3, 3))
         else:
             xf = _to_nhwc(x, torch.float32, stream)
             wp, bq = _packed(conv, xf, torch.float32, cache, stream)
             pad = conv.padding[0]
             ho, wo = hh + 2 * pad - kh + 1, ww + 2 * pad - kw + 1
             yf = torch.empty([n, cout, ho, wo], dtype=torch.float32, device=x.device)
-            nv.note_flops(_conv_flops(n, ho, wo, cout, cin, kh, kw))
-            nv.conv_igemm(nv.ptr(xf.t), nv.ptr(wp), nv.ptr(yf), nv.F32, nv.F32, n, hh, ww, xf.c_p, cout_p, cout, kh, kw,
-                          pad, ho, wo, None, nv.ptr(bq), 0, 0.0, 1.0, -1.0, 1.0, nv.NCHW, stream, x.device)
-            y = torch.empty([n, ho, wo, 2 * cout_p], dtype=torch.bfloat16, device=x.device)
-            nv.call("ic2_nchw_to_nhwc", nv.ptr(yf), nv.ptr(y), nv.BF16X3, n, cout, ho, wo, cout_p, None, stream)
+            ops.conv(xf.t, wp, yf, nv.F32, n, hh, ww, xf.c_p, cout_p, cout, (kh, kw), pad, bias=bq, out_layout=nv.NCHW,
+                     flops=_conv_flops(n, ho, wo, cout, cin, kh, kw))
+            y = ops.to_nhwc(yf, torch.bfloat16, cout_p, split=True)
         return _Act(y, cout, x3=True)
     if (dt == torch.bfloat16 and cin <= 4 and kh == 3 and kw == 3 and conv.padding[0] == 1
             and nv.pad32(cout) in (32, 64)):
@@ -170,20 +168,15 @@ def _from_rgb(conv: nn.Conv2d, x, dt, cache: dict, stream, split=False, h2=False
         fake = types.SimpleNamespace(c=cin, c_p=nv.pad32(cin))
         wp, bp = _packed(conv, fake, dt, cache, stream)
         y = torch.empty([n, hh, ww, wp.shape[0]], dtype=dt, device=x.device)
-        nv.note_flops(_conv_flops(n, hh, ww, cout, cin, kh, kw))
-        nv.call("ic2_from_rgb_conv", nv.ptr(x), cin, nv.ptr(wp), fake.c_p, nv.ptr(bp), nv.ptr(y), n, hh, ww,
-                wp.shape[0], stream)
+        ops.from_rgb_conv("", x, wp, bp, y, n, hh, ww, cin, fake.c_p, wp.shape[0],
+                          flops=_conv_flops(n, hh, ww, cout, cin, kh, kw))
         return _Act(y, cout)
     return _conv(conv, _to_nhwc(x, dt, stream), dt, cache, stream)
 
 
 def _gn_stats(norm: nn.GroupNorm, y: _Act, stream):
     """The GroupNorm (mean, rstd) of y by the separate two-stage pass (ic2_group_norm_stats) -> stats buffer."""
-    nfl = int(nv.query("ic2_group_norm_stats_floats", y.n, y.h * y.w, norm.num_groups))
-    stats = torch.empty([nfl], dtype=torch.float32, device=y.t.device)
-    nv.call("ic2_group_norm_stats", nv.ptr(y.t), nv.dtype_code(y.t.dtype), y.n, y.h * y.w, y.c_p, y.c, norm.num_groups,
-            float(norm.eps), nv.ptr(stats), stream)
-    return stats
+    return ops.gn_stats(y.t, y.n, y.h * y.w, y.c_p, y.c, norm.num_groups, norm.eps)
 
 
 def _conv_gn(conv: nn.Conv2d, norm: nn.GroupNorm, x: _Act, dt, cache: dict, stream, fuse=-1):
@@ -197,32 +190,20 @@ def _conv_gn(conv: nn.Conv2d, norm: nn.GroupNorm, x: _Act, dt, cache: dict, stre
     ho, wo = x.h + 2 * pad - kh + 1, x.w + 2 * pad - kw + 1
     # split-weight f16: the conv output stored f16 (its consumer, the f16 GroupNorm output, rounds there anyway)
     ydt = torch.float16 if x.h2 else torch.float32
-    if x.split and bool(nv.query("ic2_conv3x3_gn_fuses", x.code, x.n, x.h, x.w, x.k_p, cout_p, cout, kh, kw, pad,
-                                 norm.num_groups, int(fuse))):
+    flops = _conv_flops(x.n, ho, wo, cout, cin, kh, kw)
+    if x.split and ops.conv_gn_fuses(x.code, x.n, x.h, x.w, x.k_p, cout_p, cout, (kh, kw), pad, norm.num_groups, fuse):
         # split bf16 / split-weight f16, 64- / 128-wide layers: the 4-wave halo GEMM writes the output and the
         # statistics in one launch
         y = torch.empty([x.n, ho, wo, cout_p], dtype=ydt, device=x.t.device)
-        nfl = int(nv.query("ic2_conv3x3_gn_stats_floats", x.code, x.n, x.h, x.w, x.k_p, cout_p, kh, kw, pad,
-                           norm.num_groups))
-        stats = torch.empty([nfl], dtype=torch.float32, device=x.t.device)
-        nv.note_flops(_conv_flops(x.n, ho, wo, cout, cin, kh, kw))
-        if x.h2:
-            nv.call("ic2_conv3x3_gn_fwd_scaled", nv.ptr(x.t), nv.ptr(wp), nv.ptr(y), x.code, x.n, x.h, x.w, x.k_p,
-                    cout_p, cout, kh, kw, pad, nv.ptr(bp), _out_mul(conv, cache), norm.num_groups, float(norm.eps),
-                    nv.ptr(stats), nfl, None, 0, int(fuse), stream)
-        else:
-            nv.call("ic2_conv3x3_gn_fwd", nv.ptr(x.t), nv.ptr(wp), nv.ptr(y), x.code, x.n, x.h, x.w, x.k_p, cout_p,
-                    cout, kh, kw, pad, nv.ptr(bp), norm.num_groups, float(norm.eps), nv.ptr(stats), nfl, None, 0,
-                    int(fuse), stream)
+        stats = ops.conv_gn(x.t, wp, y, x.code, x.n, x.h, x.w, x.k_p, cout_p, cout, (kh, kw), pad, bp, norm.num_groups,
+                            norm.eps, out_mul=_out_mul(conv, cache), fuse=fuse, flops=flops)
         return _Act(y, cout), stats
     if x.split:
         # split bf16: one bf16 implicit GEMM over the tripled K (its input [hi | lo] read as [hi | hi | lo]), f32 out,
         # GroupNorm statistics on the f32 values (split-weight f16: the f16 GEMM over the doubled K)
         y = torch.empty([x.n, ho, wo, cout_p], dtype=ydt, device=x.t.device)
-        nv.note_flops(_conv_flops(x.n, ho, wo, cout, cin, kh, kw))
-        nv.conv_igemm(nv.ptr(x.t), nv.ptr(wp), nv.ptr(y), x.code, nv.dtype_code(ydt), x.n, x.h, x.w, x.k_p, cout_p,
-                      cout, kh, kw, pad, ho, wo, None, nv.ptr(bp), 0, 0.0, 1.0, -1.0, _out_mul(conv, cache), nv.NHWC,
-                      stream, x.t.device)
+        ops.conv(x.t, wp, y, x.code, x.n, x.h, x.w, x.k_p, cout_p, cout, (kh, kw), pad, bias=bp,
+                 out_mul=_out_mul(conv, cache), flops=flops)
         ya = _Act(y, cout)
         return ya, _gn_stats(norm, ya, stream)
     if dt == torch.float16:
@@ -230,16 +211,9 @@ def _conv_gn(conv: nn.Conv2d, norm: nn.GroupNorm, x: _Act, dt, cache: dict, stre
         # (ic2_conv3x3_gn_fwd takes no f16 operands)
         ya = _conv(conv, x, dt, cache, stream)
         return ya, _gn_stats(norm, ya, stream)
-    dc = nv.dtype_code(dt)
     y = torch.empty([x.n, ho, wo, cout_p], dtype=dt, device=x.t.device)
-    nfl = int(nv.query("ic2_conv3x3_gn_stats_floats", dc, x.n, x.h, x.w, x.c_p, cout_p, kh, kw, pad, norm.num_groups))
-    stats = torch.empty([nfl], dtype=torch.float32, device=x.t.device)
-    nbytes = int(nv.query("ic2_conv_igemm_ws_bytes", dc, x.n, x.h, x.w, x.c_p, cout_p, kh, kw, pad))
-    ws = torch.empty([max(nbytes, 16) // 4], dtype=torch.float32, device=x.t.device) if nbytes > 0 else None
-    nv.note_flops(_conv_flops(x.n, ho, wo, cout, cin, kh, kw))
-    nv.call("ic2_conv3x3_gn_fwd", nv.ptr(x.t), nv.ptr(wp), nv.ptr(y), dc, x.n, x.h, x.w, x.c_p, cout_p, cout, kh,
-            kw, pad, nv.ptr(bp), norm.num_groups, float(norm.eps), nv.ptr(stats), nfl, nv.ptr(ws), nbytes,
-            int(fuse), stream)
+    stats = ops.conv_gn(x.t, wp, y, nv.dtype_code(dt), x.n, x.h, x.w, x.c_p, cout_p, cout, (kh, kw), pad, bp,
+                        norm.num_groups, norm.eps, fuse=fuse, flops=flops)
     return _Act(y, cout), stats
 
 
@@ -258,39 +232,27 @@ def _group_norm_lrelu(norm: nn.GroupNorm, y: _Act, pool: bool, dt, stream, slope
     else:
         out = torch.empty([y.n, oh, ow, 2 * y.c_p if split else y.c_p], dtype=dt, device=y.t.device)
         code = nv.BF16X3 if split else nv.dtype_code(dt)
-    nv.call("ic2_gn_lrelu_pool", nv.ptr(y.t), nv.ptr(out), nv.dtype_code(y.t.dtype), code, y.n, y.h, y.w, y.c_p, y.c,
-            groups, nv.ptr(stats), nv.ptr(norm.weight), nv.ptr(norm.bias), float(slope), int(pool), stream)
+    ops.gn_lrelu_pool(y.t, out, code, y.n, y.h, y.w, y.c_p, y.c, groups, stats, norm.weight, norm.bias, slope, pool)
     return _Act(out, y.c, x3=split and not h2, h2=split and h2)
 
 
 def _gap(x: _Act, stream):
-    nfl = int(nv.query("ic2_global_avg_pool_floats", x.n, x.h * x.w, x.c_p, x.c))
-    buf = torch.empty([nfl], dtype=torch.float32, device=x.t.device)
-    nv.call("ic2_global_avg_pool", nv.ptr(x.t), nv.F16 if x.h2 else x.code, x.n, x.h * x.w, x.c_p, x.c, nv.ptr(buf),
-            stream)
+    buf = ops.gap(x.t, nv.F16 if x.h2 else x.code, x.n, x.h * x.w, x.c_p, x.c)
     return buf[: x.n * x.c].view(x.n, x.c)
 
 
 def _linear(lin: nn.Linear, x, stream, act=False, slope=0.2):
-    n = x.shape[0]
-    y = torch.empty([n, lin.out_features], dtype=torch.float32, device=x.device)
-    nv.call("ic2_fc", nv.ptr(x), x.shape[1], nv.ptr(lin.weight), nv.ptr(lin.bias), nv.ptr(y), n, lin.in_features,
-            lin.out_features, 1.0, 1.0, nv.ACT_LRELU if act else nv.ACT_LINEAR, float(slope), 1.0, stream)
-    return y
+    return ops.fc(x, x.shape[1], lin.weight, lin.bias, x.shape[0], lin.in_features, lin.out_features,
+                  act=nv.ACT_LRELU if act else nv.ACT_LINEAR, alpha=slope)
 
 
 def _to_nhwc(x, dt, stream, c_p=None):
-    n, c, h, w = x.shape
-    c_p = nv.pad32(c) if c_p is None else c_p
-    out = torch.empty([n, h, w, c_p], dtype=dt, device=x.device)
-    nv.call("ic2_nchw_to_nhwc", nv.ptr(x), nv.ptr(out), nv.dtype_code(dt), n, c, h, w, c_p, None, stream)
-    return _Act(out, c)
+    c = x.shape[1]
+    return _Act(ops.to_nhwc(x, dt, nv.pad32(c) if c_p is None else c_p), c)
 
 
 def _to_nchw(x: _Act, stream):
-    y = torch.empty([x.n, x.c, x.h, x.w], dtype=torch.float32, device=x.t.device)
-    nv.call("ic2_nhwc_to_nchw", nv.ptr(x.t), nv.dtype_code(x.t.dtype), nv.ptr(y), x.n, x.c, x.h, x.w, x.c_p, stream)
-    return y
+    return ops.to_nchw(x.t, x.n, x.c, x.h, x.w, x.c_p)
 
 
 def _check_input(x):
@@ -384,7 +346,7 @@ class HVAE_VGG_Encoder(nn.Module):
             return self.forward_train(x)
         x = _check_input(x)
         dt, split = nv.encoder_dtype(self.precision)
-        stream = nv.stream_of(x)
+        stream = _NO_STREAM
         feats = self.features_nhwc(x, dt, stream, split=split)
         n = x.shape[0]
         outs = [torch.empty([n, self.num_ws, self.w_dim], dtype=torch.float32, device=x.device) for _ in range(3)]
@@ -474,7 +436,7 @@ class VGGBlock(nn.Module):
     def forward(self, x):
         xin = x
         x = _check_input(x)
-        stream = nv.stream_of(x)
+        stream = _NO_STREAM
         y = _to_nchw(self.run_nhwc(_to_nhwc(x, torch.float32, stream), torch.float32, self._cache, stream), stream)
         return nv.refuse_backward("VGGBlock.forward", y, (xin,), (self,))
 
@@ -524,8 +486,7 @@ class HierarchyProjector(nn.Module):
         # torch.randn_like(std) on the device, in the reference's order (global, medium, fine)
         eps = torch.randn([n, self.num_ws, self.w_dim], dtype=torch.float32, device=pooled.device)
         w_out, m_out, lv_out = outs
-        nv.call("ic2_reparameterize", nv.ptr(p), nv.ptr(eps), n, self.num_ws, self.w_dim, ws_total, off, nv.ptr(w_out),
-                nv.ptr(m_out), nv.ptr(lv_out), stream)
+        ops.reparameterize(p, eps, n, self.num_ws, self.w_dim, ws_total, off, w_out, m_out, lv_out)
 
     def forward_pooled_train(self, pooled):
         """Autograd path of run_pooled (torch ops on [N, <= 512] rows): -> (w, mean, logvar)."""
@@ -542,7 +503,7 @@ class HierarchyProjector(nn.Module):
     def forward(self, x):
         xin = x
         x = _check_input(x)
-        stream = nv.stream_of(x)
+        stream = _NO_STREAM
         n = x.shape[0]
         pooled = _gap(_to_nhwc(x, torch.float32, stream), stream).contiguous()
         outs = [torch.empty([n, self.num_ws, self.w_dim], dtype=torch.float32, device=x.device) for _ in range(3)]
@@ -559,7 +520,7 @@ def quantize_uniform(w, bits=8, return_indices=False):
     idx = torch.empty(w.shape, dtype=torch.int32, device=w.device) if return_indices else None
     if w.data_ptr() % 16 or q.data_ptr() % 16:
         raise RuntimeError("quantize_uniform needs 16-byte aligned tensors")
-    nv.call("ic2_quantize_uniform", nv.ptr(w), w.numel(), int(bits), nv.ptr(q), nv.ptr(idx), nv.stream_of(w))
+    ops.quantize_uniform(w, bits, q, idx)
     return (q, idx) if return_indices else q
 
 
@@ -569,7 +530,7 @@ def _resize_fwd(img, size):
     n, c, h, w = img.shape
     oh, ow = size
     out = torch.empty([n, c, oh, ow], dtype=torch.float32, device=img.device)
-    nv.call("ic2_resize_bilinear", nv.ptr(img), nv.ptr(out), n * c, h, w, oh, ow, nv.stream_of(img))
+    ops.resize_bilinear(img, out, n * c, h, w, oh, ow)
     return out
 
 

@@ -32,6 +32,32 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.ic2_abi_version() == 1
 
 
+def test_ctypes_table_matches_every_declaration():
+    """For every function include/ic2ops.h declares, _native._SIGS / _RESTYPE are what the declaration implies: a
+    pointer -> c_void_p, int / int64_t / uint64_t / float / double by value, a `const char*` result -> c_char_p."""
+    import ctypes
+    by_value = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+                "double": ctypes.c_double}
+    src = open(os.path.join(ROOT, "include", "ic2ops.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    decls = re.findall(r"^\s*(const char\s*\*|int64_t|int)\s+(ic2_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M)
+    assert sorted(d[1] for d in decls) == _declared_symbols(), "a declaration the parser does not understand"
+    checked = 0
+    for ret, name, params in decls:
+        if name == "ic2_last_error":   # bound by hand in load()
+            continue
+        params = [p.strip() for p in params.split(",")]
+        if params == ["void"]:
+            params = []
+        want = [ctypes.c_void_p if "*" in p else by_value[p.rsplit(" ", 1)[0].replace("const ", "").strip()]
+                for p in params]
+        assert nv._SIGS[name] == want, name
+        want_ret = ctypes.c_char_p if "char" in ret else by_value[ret]
+        assert nv._RESTYPE.get(name, ctypes.c_int) is want_ret, name
+        checked += 1
+    assert checked == len(nv._SIGS) >= 78
+
+
 def test_integration_index_lists_every_entry_point():
     """INTEGRATION.md's entry-point index names every function the header declares (`x`(`_floats`) names both)."""
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
