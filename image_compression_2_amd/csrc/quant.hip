@@ -254,7 +254,9 @@ __device__ __forceinline__ void gumbel_row(float v, int64_t i, const float (&c)[
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
   row.inv_s = 1.f / s;
   row.ymax = ymax;
-  row.imin = imin;
+  // a NaN or infinite latent: no distance compares below INFINITY in any lane.  torch.argmin gives 0 there (all
+  // distances NaN, or all equal), and so does codebook_argmin_kernel; a finite latent never leaves the start value
+  row.imin = imin == 0x7fffffff ? 0 : imin;
   row.iymax = iymax;
 }
 

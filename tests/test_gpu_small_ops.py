@@ -12,15 +12,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from guarded import Guarded, _bits, _nan_bits, _same_bits
 from image_compression_2_amd import _native as nv
 from oracle import sg3
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24      # unit roundoff of f32 (half an ulp of a value in [1, 2))
-GUARD = 64          # guard elements on each side of an output (keeps the slice 16-byte aligned)
-_INT = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
-_SENT = {2: 0x5A5A, 4: 0x5A5AA5A5, 8: 0x5A5AA5A55A5AA5A5}
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 
 
@@ -28,42 +26,6 @@ DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 def _no_grad():
     with torch.no_grad():
         yield
-
-
-def _bits(t):
-    """The tensor's storage as integers of the same width (bitwise comparisons, NaN included)."""
-    return t.view(_INT[t.element_size()])
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(_bits(a.contiguous()), _bits(b.contiguous()))
-
-
-class Guarded:
-    """`numel` elements of `dtype` (NaN for float types, `fill` otherwise) between two sentinel-filled guards."""
-
-    def __init__(self, numel, dtype, device, fill=None):
-        numel = int(numel)
-        self.numel = numel
-        self.buf = torch.empty([numel + 2 * GUARD], dtype=dtype, device=device)
-        _bits(self.buf).fill_(_SENT[self.buf.element_size()])
-        self.t = self.buf[GUARD:GUARD + numel]
-        self.t.fill_(float("nan") if dtype.is_floating_point else fill)
-        assert self.t.data_ptr() % 16 == 0
-
-    def ptr(self):
-        return nv.ptr(self.t)
-
-    def intact(self):
-        b = _bits(self.buf)
-        s = _SENT[self.buf.element_size()]
-        return bool((b[:GUARD] == s).all().item()) and bool((b[GUARD + self.numel:] == s).all().item())
-
-
-def _nan_bits(t):
-    """True where the element still holds the NaN prefill of Guarded, bit for bit."""
-    ref = torch.full([1], float("nan"), dtype=t.dtype, device=t.device)
-    return _bits(t) == _bits(ref)
 
 
 def _gen(seed):
