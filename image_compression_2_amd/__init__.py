@@ -11,6 +11,9 @@ Drop-in classes (same names / signatures as the reference modules):
   metrics:                    uint8_quality, ssim, evaluate_compression (the PSNR + SSIM record of test_compression);
                               ms_ssim_terms, uint8_ms_ssim, ms_ssim (the MS-SSIM figure), ms_ssim_loss, MSSSIMLoss
                               (1 - MS-SSIM with a HIP backward: the perceptual training term that works offline)
+  image_io:                   resize_u8 / to_tensor (Pillow's 8-bit Resize + ToTensor + Normalize, bit for bit, on
+                              ragged uint8 batches), to_uint8 / save_images (the three f32 -> uint8 conversions),
+                              ImageDataset, image_batches (the reference's dataset with the transform on the device)
 All compute runs in libic2ops.so (hand-written HIP for gfx950); ROCm tensors only.
 """
 from . import _native  # noqa: F401
@@ -24,10 +27,15 @@ from .cabac_compression import CABACCompressor, ContextModel, cabac_encode, caba
 from . import legacy  # noqa: F401
 from .metrics import uint8_quality, ssim, ssim_from_sums, evaluate_compression  # noqa: F401
 from .metrics import ms_ssim_terms, uint8_ms_ssim, ms_ssim, ms_ssim_loss, MSSSIMLoss, MS_SSIM_TILE  # noqa: F401
+from . import image_io  # noqa: F401
+from .image_io import (resample_tables, resize_u8, to_tensor, to_uint8, save_images, ImageDataset,  # noqa: F401
+                       image_batches)
 
 __all__ = ["HVAE_VGG_Encoder", "VGGBlock", "HierarchyProjector", "StyleGAN3Compressor", "save_tensor_as_image",
            "GumbelSoftmaxDiscretization", "GumbelSoftmaxCompressor", "Generator", "SynthesisNetwork",
            "SynthesisLayer", "SynthesisInput", "MappingNetwork", "FullyConnectedLayer", "make_generator", "SG3_R_KWARGS",
            "quantize_uniform", "resize_bilinear", "sg3_ops", "CABACCompressor", "ContextModel", "cabac_encode",
            "cabac_decode", "legacy", "uint8_quality", "ssim", "ssim_from_sums", "evaluate_compression",
-           "ms_ssim_terms", "uint8_ms_ssim", "ms_ssim", "ms_ssim_loss", "MSSSIMLoss", "MS_SSIM_TILE"]
+           "ms_ssim_terms", "uint8_ms_ssim", "ms_ssim", "ms_ssim_loss", "MSSSIMLoss", "MS_SSIM_TILE",
+           "image_io", "resample_tables", "resize_u8", "to_tensor", "to_uint8", "save_images", "ImageDataset",
+           "image_batches"]

@@ -23,6 +23,8 @@ F32, BF16, F16, BF16X3, F16X2 = 0, 1, 2, 3, 4
 F16_IEEE = 5   # out_dtype only: f16 output converted IEEE (overflow -> inf), the training path's gradient convs
 ACT_LINEAR, ACT_LRELU = 0, 1
 NHWC, NCHW, NHWC16 = 0, 1, 2
+RESAMPLE_BILINEAR, RESAMPLE_BICUBIC, RESAMPLE_LANCZOS = 0, 1, 2   # ic2ops.h IC2_RESAMPLE_*
+U8_EVAL, U8_SAVE_IMAGE, U8_REFERENCE = 0, 1, 2                    # ic2ops.h IC2_U8_*
 
 
 def act_in_layout(layout):
@@ -106,6 +108,10 @@ _SIGS = {
     "ic2_ms_ssim_bwd_ws_floats": [_I64, _I, _I, _I],
     "ic2_ms_ssim_bwd": [_P, _P, _I, _P, _P, _I64, _I, _I, _I, _P, _P, _P, _P],
     "ic2_resize_bilinear": [_P, _P, _I64, _I, _I, _I, _I, _P],
+    "ic2_resample_ksize": [_I, _I, _I],
+    "ic2_resample_coeffs": [_I, _I, _I, _P, _P],
+    "ic2_resample_u8": [_P, _P, _P, _I, _I, _I, _I, _I, _I64, _P, _I64, _P, _P, _P],
+    "ic2_image_to_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
     "ic2_rc_bound": [_I64, _I64],
     "ic2_rc_encode": [_P, _I64, _I, _I, _I, _P, _I64, _P, _I],
     "ic2_rc_decode": [_P, _P, _I64, _I, _I, _I, _P, _I],

@@ -508,3 +508,28 @@ def gumbel_quantize_bwd(z, codebook, logt, seed, noise, g, q, want_dlogt):
         dlogt = _empty(1, _F32, dev)
     nv.call(fn, *args, _dp(dz), _dp(dlogt), _dp(ws), nbytes, nv.stream_of(z))
     return dz, dlogt
+
+
+# ------------------------------------------------------------------------------------------------ image I/O
+def resample_u8(src, recs, tables, ws, out, n, c, oh, ow, max_rows, total_rows, *, lut=None):
+    """Pillow's 8-bit resize of a ragged uint8 HWC batch in two launches (ic2_resample_u8): src the packed sources,
+    recs [n][9] int64 device records, tables the int32 table blob, ws >= total_rows * ow * c bytes -> out uint8
+    [n][oh][ow][c], or with lut [c][256] f32 out f32 [n][c][oh][ow] = lut[ch][value]."""
+    fn, dev = "ic2_resample_u8", src.device
+    u8 = torch.uint8
+    nv.call(fn, _p(fn, "src", src, dev, 1, u8), _p(fn, "recs", recs, dev, 9 * n, torch.int64),
+            _p(fn, "tables", tables, dev, 1, torch.int32), n, c, oh, ow, max_rows, total_rows,
+            _p(fn, "ws", ws, dev, total_rows * ow * c, u8), ws.numel(),
+            _p(fn, "out", out, dev, n * oh * ow * c, u8 if lut is None else _F32),
+            _p(fn, "lut", lut, dev, c * 256, opt=True), nv.stream_of(src))
+    return out
+
+
+def image_to_u8(x, y, n, c, h, w_, mode):
+    """f32 NCHW x [n][c][h][w] -> uint8 NHWC y [n][h][w][c] in one of the reference's three conversions
+    (ic2_image_to_u8; mode nv.U8_EVAL / U8_SAVE_IMAGE / U8_REFERENCE)."""
+    fn, dev = "ic2_image_to_u8", x.device
+    need = n * c * h * w_
+    nv.call(fn, _p(fn, "x", x, dev, need), _p(fn, "y", y, dev, need, torch.uint8), n, c, h, w_, int(mode),
+            nv.stream_of(x))
+    return y

@@ -437,6 +437,53 @@ int ic2_ms_ssim_bwd(const float* a, const float* b, int mode, const float* ws_fw
  * (stylegan3_hvae_full.py:277-279), NCHW f32. */
 int ic2_resize_bilinear(const float* x, float* y, int64_t nc, int h, int w, int oh, int ow, void* stream);
 
+/* ---- image I/O: the uint8 ends of the reference's snippets --------------------------------------------------
+ * transforms.Resize on a PIL image is PIL.Image.resize, whose 8-bit resampler is integer arithmetic on fixed-point
+ * coefficients; the three entry points below restate it bit for bit on "L" (c = 1) and "RGB" (c = 3) images.
+ *
+ * ic2_resample_ksize, ic2_resample_coeffs (HOST only, no GPU): one axis' coefficient table for `in` samples -> `out`
+ * outputs, sizes 1 .. 16384.  filter_support = 1 / 2 / 3 (triangle; Keys cubic, a = -0.5; sinc(x) sinc(x / 3) on
+ * [-3, 3)); scale = in / out, fs = max(scale, 1), support = filter_support * fs, ksize = (int)ceil(support) * 2 + 1.
+ * Output xx: center = (xx + 0.5) * scale, xmin = max(0, (int)(center - support + 0.5)), taps = min(in, (int)(center +
+ * support + 0.5)) - xmin, w[x] = f((x + xmin - center + 0.5) / fs) divided by the taps' sum (summed in index order)
+ * when that is not 0; kk[xx][x] = (int)(w * 2^22 +- 0.5) (half away from zero), 0 for x >= taps; bounds[xx] = (xmin,
+ * taps).  Doubles, libm's sin, one rounding per written operation.  ic2_resample_ksize returns 0 for a size outside
+ * the range or an unknown filter; ic2_resample_coeffs IC2_E_INVALID for those and for a null pointer. */
+enum { IC2_RESAMPLE_BILINEAR = 0, IC2_RESAMPLE_BICUBIC = 1, IC2_RESAMPLE_LANCZOS = 2 };
+int ic2_resample_ksize(int in, int out, int filter);
+int ic2_resample_coeffs(int in, int out, int filter, int32_t* bounds /*[out][2]*/, int32_t* kk /*[out][ksize]*/);
+
+/* transforms.Resize((oh, ow), interpolation) [+ ToTensor + Normalize] of ImageDataset (stylegan3_hvae_full.py:
+ * 969-973) and of the README quick start, for a ragged batch in two launches.  src: one device blob of uint8 HWC
+ * images of c channels, any sizes; recs: n DEVICE records of 9 int64,
+ *   {src_off, h, w, xtab, ytab, kx, ky, ws_off, y0}
+ * src_off / ws_off in bytes; xtab / ytab: offset in int32s into `tables` of the axis' table, bounds [out][2]
+ * followed by kk [out][ksize] (ic2_resample_coeffs; an axis whose size does not change is not filtered by Pillow and
+ * takes the identity table, bounds (xx, 1), kk 2^22, ksize 1); kx, ky the two ksizes; y0 = ymin(0), the first source
+ * row the vertical pass reads.  The records are the caller's word: they are read on the device only.
+ * Pass 1 filters along x the rows y0 .. ymin(oh-1) + taps(oh-1) - 1 of each image: acc = 2^21 + sum p * k in int32,
+ * clip(acc >> 22, 0, 255) as uint8 to ws[ws_off + (row - y0) * ow * c ..].  Pass 2 filters along y the same way and
+ * stores uint8 HWC out[n][oh][ow][c] when lut is NULL, else f32 NCHW out[n][c][oh][ow] = lut[ch][value], lut [c][256]
+ * f32 on the device (ToTensor + Normalize as a table).  max_rows: the largest row count of one image (pass 1's
+ * grid); total_rows: their sum; ws_bytes >= total_rows * ow * c.
+ * IC2_E_INVALID, before any launch: null pointer (lut excepted), n outside [1, 65535], c not 1 or 3, oh / ow outside
+ * [1, 16384], max_rows outside [1, 16384], total_rows outside [max_rows, n * max_rows], workspace too small.  (The
+ * filter is a property of the tables: an unknown one is refused where they are built, ic2_resample_coeffs.) */
+int ic2_resample_u8(const uint8_t* src, const int64_t* recs, const int32_t* tables, int n, int c, int oh, int ow,
+                    int max_rows, int64_t total_rows, uint8_t* ws, int64_t ws_bytes, void* out, const float* lut,
+                    void* stream);
+
+/* The model's f32 NCHW output x [n][c][h][w] (nominal [-1, 1]) as uint8 NHWC y [n][h][w][c], the three ways the
+ * reference does it; f32, one rounding per written operation:
+ *   IC2_U8_EVAL       hvae_training.py:368-388 (the metric kernels' conversion): trunc(clamp(x*0.5 + 0.5, 0, 1) * 255)
+ *   IC2_U8_SAVE_IMAGE torchvision.utils.save_image((x + 1) / 2) of the README: trunc(clamp((x+1)/2 * 255 + 0.5, 0, 255))
+ *   IC2_U8_REFERENCE  save_tensor_as_image (stylegan3_hvae_full.py:924-933): trunc((x + 1) * 127.5), saturated to
+ *                     0 / 255 outside [0, 256) (where NumPy's cast is undefined)
+ * NaN -> 0 in every mode.  Only IC2_U8_SAVE_IMAGE inverts ToTensor + Normalize(0.5, 0.5) on all 256 codes; the other
+ * two return 63 codes one lower.  IC2_E_INVALID: null pointer, non-positive size, unknown mode, c * h * w >= 2^31 - 4. */
+enum { IC2_U8_EVAL = 0, IC2_U8_SAVE_IMAGE = 1, IC2_U8_REFERENCE = 2 };
+int ic2_image_to_u8(const float* x, uint8_t* y, int n, int c, int h, int w, int mode, void* stream);
+
 /* ---- entropy coding of the codebook indices (HOST pointers; no GPU) ----------------------------------------
  * Replaces the reference's CABAC stage (cabac_compression.py:60-406: ContextModel, ArithmeticCoder,
  * cabac_encode / cabac_decode; non-functional there) with a context-adaptive binary range coder:
